@@ -3,8 +3,13 @@
 GB/s) of the TPC-H Q1 lineitem scan->filter->aggregate hot path on MI355X.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`. One rank per GPU
-(torchrun for N>1; reads RANK/LOCAL_RANK/WORLD_SIZE). A "step" is one full
-pass of the hot path over the synthetic workload: fused GPU
+(torchrun for N>1; reads RANK/LOCAL_RANK/WORLD_SIZE). A plain run does only
+what the headline figure needs: generate + stage the workload, W warmups, K
+timed steps, one JSON line. `--full` adds the legs that take runs of their
+own (rocprofv3 TCC-traffic child run, CPU baseline). `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy.
+
+A "step" is one full pass of the hot path over the synthetic workload: fused GPU
 scan->filter->group-by over the rank's microblock shard + the partial-
 aggregate exchange across ranks (the reference's 2-phase group-by exchange;
 SURVEY.md §2 collective inventory) + local merge. W untimed warmups, exactly
@@ -17,7 +22,8 @@ Weak scaling: each rank owns a full per-GPU shard of --rows rows (row-range
 sharded generation is byte-deterministic).
 
 Inputs are resident in HBM before the timed region starts (staged once at
-load). The oracle appears ONLY in the cpu_baseline leg (rank 0, N=1).
+load). The oracle appears ONLY in the cpu_baseline leg (--full, rank 0,
+N=1).
 """
 import argparse
 import ctypes as C
@@ -144,8 +150,7 @@ def measure_traffic(args):
                "--output-format", "csv", "-d", td, "--", sys.executable, me,
                "--workload", args.workload, "--rows", str(args.rows or 0),
                "--block-bytes", str(args.block_bytes),
-               "--seed", str(args.seed), "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-traffic"]
+               "--seed", str(args.seed), "--steps", "2", "--warmup", "1"]
         env = dict(os.environ, TMPDIR=td)
         try:
             subprocess.run(cmd, cwd=td, env=env, check=True,
@@ -185,6 +190,68 @@ def measure_traffic(args):
                     launches=n)
 
 
+DUMP_MAX_BYTES = 48 << 20  # per array; the whole dump stays under 64 MB
+
+
+def _capped(arr, seed):
+    """float64 copy of `arr`; a fixed seeded sample when it is too large."""
+    arr = np.asarray(arr).reshape(-1)
+    cap = DUMP_MAX_BYTES // 8
+    if arr.size > cap:
+        idx = np.sort(np.random.default_rng(seed).choice(
+            arr.size, size=cap, replace=False))
+        arr = arr[idx]
+    return arr.astype(np.float64)
+
+
+def dump_outputs(dirpath, out, n_aggs, seed, bitmap=None):
+    """Write what the timed path returned in its last step as float64 .npy
+    files. Aggregating workloads: the result table (group keys, row counts,
+    aggregate cells, scanned/passed row counts); `out` is an AggResult or
+    merge_results' tuple. Filter workloads: the survivor count and the
+    result bitmap the caller fetches.
+
+    Wide-int cells do not fit a float64, so they are written twice:
+    agg_values (rounded, for tolerance compares) and agg_limbs32 (the 256-bit
+    two's complement value as eight exact 32-bit limbs, low limb first)."""
+    os.makedirs(dirpath, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+
+    if bitmap is not None:
+        save("survivors", np.array([out], dtype=np.float64))
+        pad = (-bitmap.size) % 4
+        words = np.concatenate(
+            [bitmap, np.zeros(pad, dtype=np.uint8)]).view("<u4")
+        save("bitmap_words32", _capped(words, seed))
+        return
+    if isinstance(out, tuple):
+        groups, scanned, passed = out
+        rows = [(k, v[0], v[1:]) for k, v in groups.items()]
+    else:
+        scanned, passed = out.rows_scanned, out.rows_passed
+        rows = abi.result_rows(out, n_aggs)
+    klen = max([len(k) for k, _, _ in rows] + [1])
+    keys = np.full((len(rows), klen), -1.0)
+    counts = np.zeros(len(rows))
+    values = np.zeros((len(rows), n_aggs))
+    limbs = np.zeros((len(rows), n_aggs, 8))
+    for i, (key, cnt, cells) in enumerate(rows):
+        keys[i, :len(key)] = list(key)
+        counts[i] = cnt
+        for a, c in enumerate(cells):
+            c = int(c or 0)
+            values[i, a] = float(c)
+            u = c & ((1 << 256) - 1)
+            limbs[i, a] = [(u >> (32 * j)) & 0xFFFFFFFF for j in range(8)]
+    save("rows_scanned_passed", np.array([scanned, passed], dtype=np.float64))
+    save("group_keys", keys)
+    save("group_row_counts", counts)
+    save("agg_values", values)
+    save("agg_limbs32", limbs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -195,13 +262,22 @@ def main():
                     help="rows per GPU (default: workload's full size)")
     ap.add_argument("--block-bytes", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: "
+                         "rocprofv3 TCC-traffic child run + CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the rocprofv3 TCC-traffic leg")
+                    help="with --full: skip the rocprofv3 TCC-traffic leg")
     ap.add_argument("--trace", action="store_true",
                     help="per-step device-time table (prep/main kernel) — "
                          "the per-operator monitor rebuild (SURVEY §5)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
@@ -261,8 +337,7 @@ def main():
                 return merged
             return res
         else:
-            eng.filter(h, filt, want_row_ids=False)
-            return None
+            return eng.filter(h, filt, want_row_ids=False)
 
     def barrier_sync():
         if dist is not None:
@@ -271,6 +346,7 @@ def main():
 
     kernel_ms = []
     prep_ms = []
+    last_out = None
     for _ in range(args.warmup):
         one_step()
     jit = eng.last_jit()
@@ -278,7 +354,7 @@ def main():
     t_start = time.time()
     for _ in range(args.steps):
         t_step = time.time()
-        one_step()
+        last_out = one_step()
         kernel_ms.append(eng.last_kernel_ms())
         prep_ms.append(eng.last_prep_ms())
         if args.trace and rank == 0:
@@ -296,6 +372,10 @@ def main():
             t = t.cuda(device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.cpu().item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, n_aggs, args.seed,
+                     bitmap=eng.fetch_bitmap(h) if agg is None else None)
 
     total_rows = rows_per_gpu * n_gpus
     ms_per_step = elapsed / args.steps * 1000.0
@@ -318,7 +398,7 @@ def main():
 
     # --- measured HBM traffic (TCC fabric counters, separate rocprofv3
     #     child run of the same workload; per launch of the main kernel) ----
-    if rank == 0 and world <= 1 and not args.no_traffic \
+    if args.full and rank == 0 and world <= 1 and not args.no_traffic \
             and os.environ.get("OBX_BENCH_TRAFFIC", "1") != "0":
         tr = measure_traffic(args)
         if tr is not None:
@@ -333,7 +413,7 @@ def main():
     #     N=1). The oracle is -O3 -march=native auto-vectorized C, not the
     #     reference's hand-written AVX512 — stated in `sample`. ------------
     cpu_baseline = None
-    if rank == 0 and world <= 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world <= 1 and not args.no_cpu_baseline:
         cores = os.cpu_count() or 1
         rpb = max(li.total_rows // li.n_blocks, 1)
         nblk = min(max(int(150_000_000 // rpb), 1), li.n_blocks)
