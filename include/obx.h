@@ -369,6 +369,9 @@ double obx_gpu_last_prep_ms(obx_gpu_ctx *ctx);
 /* 1 if the last scan_filter_agg ran the hipRTC plan-specialized kernel
  * (query codegen), 0 if the precompiled generic kernels ran. */
 int obx_gpu_last_jit(obx_gpu_ctx *ctx);
+/* workgroups the last scan_filter_agg launched its plan-specialized kernel
+ * with (0 when the generic kernels ran). */
+uint32_t obx_gpu_last_grid(obx_gpu_ctx *ctx);
 uint64_t obx_gpu_total_rows(obx_gpu_ctx *ctx, int handle);
 uint64_t obx_gpu_total_bytes(obx_gpu_ctx *ctx, int handle);
 uint64_t obx_gpu_last_survivors(obx_gpu_ctx *ctx, int handle);

@@ -16,6 +16,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 #include <algorithm>
 
@@ -82,6 +83,8 @@ extern "C" __global__ void k_lower_leaves(
     uint32_t, const int64_t *, blk_leaf *);
 extern "C" __global__ void k_col_minmax(
     const uint8_t *, const dev_block *, uint32_t, uint32_t, int64_t *);
+extern "C" __global__ void k_gtable_init(
+    unsigned long long *, uint32_t, uint32_t, uint32_t, uint32_t);
 
 #define HIP_TRY(x)                                        \
   do {                                                    \
@@ -126,6 +129,20 @@ struct obx_handle {
      1 dict, 2 intdiff, 3 const, 4 slow), bit4 = string; col_cnt = dict
      count capped at 255 */
   std::vector<uint8_t> col_class, col_cnt;
+  /* per-column folds of col_class / col_cnt (summarize_col_classes, at
+     load): everything the per-query plan and JIT eligibility tests ask of
+     the per-block arrays, so a query costs O(columns), not O(blocks) */
+  bool col_span_any[OBX_DEV_MAX_COLS] = {};    /* class 5 in any block */
+  bool col_grp16_every[OBX_DEV_MAX_COLS] = {}; /* class 1 and count < 16 in
+                                                  every block */
+  bool col_slow_any[OBX_DEV_MAX_COLS] = {};    /* class > 3 or string in
+                                                  any block */
+  uint32_t col_cnt_max[OBX_DEV_MAX_COLS] = {}; /* max of col_cnt */
+  /* max over blocks of (cnt[c0]+1)*(cnt[c1]+1), filled on the first query
+     that groups by (c0, c1) and whose product of column maxima exceeds the
+     16-cell limit (key = c0 << 16 | c1) */
+  mutable std::map<uint32_t, uint32_t> pair_cells_max;
+  uint32_t n_cus = 256; /* compute units of the owning device */
   /* stored skip index: per-(block,col) [min,max] of non-null decoded
      values, captured by k_col_minmax at load (device copy feeds
      k_lower_leaves pruning; host summary feeds the JIT's i64-accumulator
@@ -166,8 +183,17 @@ struct obx_gpu_ctx {
   double last_ms = 0.0;
   double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
   int last_jit = 0;           /* last scan used the specialized kernel */
+  uint32_t last_grid = 0;     /* workgroups that kernel was launched with */
+  uint32_t n_cus = 256;
+  /* pinned landing buffer for the group table + counters of a scan (sized
+     for the growth-path table) */
+  uint8_t *h_result = nullptr;
   std::vector<obx_handle> handles;
 };
+
+/* device words after the group table that hold the 16 scan counters: one
+   allocation, so one copy fetches both */
+#define OBX_RESULT_BYTES(slots) (sizeof(gslot) * (slots) + 16 * 8)
 
 extern "C" int obx_gpu_open(int device, obx_gpu_ctx **out) {
   int n = 0;
@@ -181,6 +207,14 @@ extern "C" int obx_gpu_open(int device, obx_gpu_ctx **out) {
   HIP_TRY(hipEventCreate(&ctx->ev_stop));
   HIP_TRY(hipEventCreate(&ctx->ev_p0));
   HIP_TRY(hipEventCreate(&ctx->ev_p1));
+  {
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (prop.multiProcessorCount > 0)
+      ctx->n_cus = (uint32_t)prop.multiProcessorCount;
+  }
+  HIP_TRY(hipHostMalloc((void **)&ctx->h_result,
+                        OBX_RESULT_BYTES(OBX_GTABLE_BIG), hipHostMallocDefault));
   *out = ctx;
   return OBX_SUCCESS;
 }
@@ -191,7 +225,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   for (auto &h : ctx->handles) {
     if (!h.in_use) continue;
     (void)hipFree(h.d_buf); (void)hipFree(h.d_blocks); (void)hipFree(h.d_bleaves);
-    (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_counters); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
+    (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
     (void)hipFree(h.d_bitmap); (void)hipFree(h.d_row_ids); (void)hipFree(h.d_blk_counts);
     (void)hipFree(h.d_row_slot); (void)hipFree(h.d_minmax);
     for (auto *p : h.d_decode_out) (void)hipFree(p);
@@ -199,6 +233,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   (void)hipStreamDestroy(ctx->stream);
   (void)hipEventDestroy(ctx->ev_start);
   (void)hipEventDestroy(ctx->ev_stop);
+  (void)hipHostFree(ctx->h_result);
   delete ctx;
   return OBX_SUCCESS;
 }
@@ -224,6 +259,60 @@ static uint64_t host_crc32c(const uint8_t *buf, int64_t len) {
 static uint32_t grid_for(uint32_t n_blocks) {
   uint32_t g = n_blocks < 4096u ? n_blocks : 4096u;
   return g ? g : 1;
+}
+
+/* grid of the persistent scan JIT (obx_jit_v2.inc): OBX_JIT_GRID_WAVES
+   times what is resident at wpb workgroups per CU, and never more
+   workgroups than blocks. Each workgroup flushes once, a handful of global
+   atomics per live cell, so the grid is free to be finer than the resident
+   set: the dispatcher then evens out CU-to-CU differences and the tail
+   shrinks to one short workgroup. Measured on Q1 SF=100 (profiles/
+   r03_q1_flush.md): 1x 3.00 ms, 2x 2.90, 4x 2.80, 8x 2.76, 12x 2.78,
+   16x 2.82, 32x 3.70; 1.5x (a half-empty second wave) 3.22. The one
+   source of that grid: the strategy proves its i64 accumulator bound for
+   it and the launch uses it. */
+#define OBX_JIT_GRID_WAVES 8
+static uint32_t jit_grid_for(uint32_t n_blocks, uint32_t n_cus, int wpb) {
+  uint64_t g = (uint64_t)(n_cus ? n_cus : 1) * (uint32_t)(wpb > 0 ? wpb : 1) *
+               OBX_JIT_GRID_WAVES;
+  if (g > n_blocks) g = n_blocks;
+  return g ? (uint32_t)g : 1;
+}
+
+/* device-side fill of an empty group table (EMPTY keys, zero cells, MIN/MAX
+   sentinels by aggregate mask) and of the tail_words counters behind it */
+static void gtable_init(gslot *gt, uint32_t n_slots, uint32_t tail_words,
+                        uint32_t min_mask, uint32_t max_mask,
+                        hipStream_t stream) {
+  const uint32_t words =
+      n_slots * (uint32_t)(sizeof(gslot) / 8) + tail_words;
+  hipLaunchKernelGGL(k_gtable_init, dim3((words + OBX_WG_HOST - 1) / OBX_WG_HOST),
+                     dim3(OBX_WG_HOST), 0, stream, (unsigned long long *)gt,
+                     n_slots, tail_words, min_mask, max_mask);
+}
+
+/* fold the per-(block,col) class/count arrays into the per-column facts
+   build_plan and jit_blocks_ok test; every loader calls this once */
+static void summarize_col_classes(obx_handle &h) {
+  const uint32_t nc = h.n_cols;
+  for (uint32_t c = 0; c < nc; c++) {
+    h.col_span_any[c] = h.col_slow_any[c] = false;
+    h.col_grp16_every[c] = true;
+    h.col_cnt_max[c] = 0;
+  }
+  h.pair_cells_max.clear();
+  const size_t nb = nc ? h.col_class.size() / nc : 0;
+  for (size_t b = 0; b < nb; b++) {
+    const uint8_t *cls = &h.col_class[b * nc];
+    const uint8_t *cnt = &h.col_cnt[b * nc];
+    for (uint32_t c = 0; c < nc; c++) {
+      const uint8_t k = cls[c];
+      if ((k & 0xF) == 5) h.col_span_any[c] = true;
+      if ((k & 0xF) != 1 || cnt[c] >= 16) h.col_grp16_every[c] = false;
+      if ((k & 0xF) > 3 || (k & 0x10)) h.col_slow_any[c] = true;
+      if (cnt[c] > h.col_cnt_max[c]) h.col_cnt_max[c] = cnt[c];
+    }
+  }
 }
 
 /* ---- host block parsing (mirrors ObMicroBlockDecoder pointer math,
@@ -532,6 +621,8 @@ extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
   }
   h.total_rows = row_start;
   h.lds_ok = lds_ok;
+  h.n_cus = ctx->n_cus;
+  summarize_col_classes(h);
   /* dict stability: identical dict payload in every block enables the
      JIT's persistent (whole-kernel) histograms/value tables */
   for (uint16_t c = 0; c < bs->n_cols; c++) {
@@ -553,8 +644,8 @@ extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
   HIP_TRY(hipMalloc(&h.d_blocks, sizeof(dev_block) * bs->n_blocks));
   HIP_TRY(hipMemcpy(h.d_blocks, blocks.data(),
                     sizeof(dev_block) * bs->n_blocks, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h.d_counters, 16 * sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc(&h.d_gtable, sizeof(gslot) * OBX_GTABLE_SLOTS));
+  HIP_TRY(hipMalloc(&h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS)));
+  h.d_counters = (unsigned long long *)(h.d_gtable + OBX_GTABLE_SLOTS);
   HIP_TRY(hipMalloc(&h.d_pleaves, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES));
 
   /* stored skip index: capture per-(block,col) min/max once at load
@@ -598,7 +689,7 @@ extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
   obx_handle &h = ctx->handles[handle];
   if (!h.in_use) return OBX_INVALID_ARGUMENT;
   (void)hipFree(h.d_buf); (void)hipFree(h.d_blocks); (void)hipFree(h.d_bleaves);
-  (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_counters); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
+  (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
   (void)hipFree(h.d_bitmap); (void)hipFree(h.d_row_ids); (void)hipFree(h.d_blk_counts);
   (void)hipFree(h.d_row_slot); (void)hipFree(h.d_minmax);
   for (auto *&p : h.d_decode_out) { (void)hipFree(p); p = nullptr; }
@@ -772,14 +863,9 @@ static int build_plan(const obx_handle &h, const obx_filter_desc *filter,
     /* group keys decode via col_value (no block context): COLUMN_EQUAL
        group columns would misdecode — reject them (value/filter columns
        on COLUMN_EQUAL are fully supported via col_value2) */
-    if (!h.col_class.empty()) {
-      for (uint32_t g = 0; g < ph.n_group_cols; g++) {
-        uint16_t col = ph.need_cols[ph.group_idx[g]];
-        for (uint32_t b2 = 0; b2 < h.n_blocks; b2++)
-          if ((h.col_class[(size_t)b2 * h.n_cols + col] & 0xF) == 5)
-            return OBX_NOT_SUPPORTED;
-      }
-    }
+    for (uint32_t g = 0; g < ph.n_group_cols; g++)
+      if (h.col_span_any[ph.need_cols[ph.group_idx[g]]])
+        return OBX_NOT_SUPPORTED;
   }
   /* group aggregates into row passes: aggs whose inputs fit in <=3 shared
      decoded columns run together (COUNT(*) needs no pass — filled from the
@@ -1068,23 +1154,17 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
   int rc = prep_query(ctx, h, filter, agg, ph, plv);
   if (rc != OBX_SUCCESS) return rc;
   ctx->last_jit = 0;
+  ctx->last_grid = 0;
 
-  /* init global table (min/max cells need INT64_MAX/MIN) */
-  std::vector<gslot> init(OBX_GTABLE_SLOTS);
-  memset(init.data(), 0, sizeof(gslot) * OBX_GTABLE_SLOTS);
-  for (auto &s : init) {
-    s.key = OBX_KEY_EMPTY;
-    for (uint32_t a = 0; a < ph.n_aggs; a++) {
-      if (ph.aggs[a].kind == OBX_AGG_MIN)
-        s.cells[a][0] = (unsigned long long)INT64_MAX;
-      else if (ph.aggs[a].kind == OBX_AGG_MAX)
-        s.cells[a][0] = (unsigned long long)INT64_MIN;
-    }
+  /* init global table + counters on the device (min/max cells need
+     INT64_MAX/MIN) */
+  uint32_t min_mask = 0, max_mask = 0;
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (ph.aggs[a].kind == OBX_AGG_MIN) min_mask |= 1u << a;
+    else if (ph.aggs[a].kind == OBX_AGG_MAX) max_mask |= 1u << a;
   }
-  HIP_TRY(hipMemcpyAsync(h.d_gtable, init.data(),
-                         sizeof(gslot) * OBX_GTABLE_SLOTS,
-                         hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipMemsetAsync(h.d_counters, 0, 16 * 8, ctx->stream));
+  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, min_mask, max_mask,
+              ctx->stream);
 
   /* Default: the fused single-kernel path (measured fastest in round 1).
      OBX_PIPELINE_AGG=1 switches to the filter->group->agg-pass kernel DAG
@@ -1130,7 +1210,7 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     ctx->last_jit = je ? g_jit_kind : 0; /* 2 = persistent v2, 1 = v1 */
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     if (je) {
-      if (jit_launch(je, h, grid_for(h.n_blocks), ctx->stream) != 0)
+      if (jit_launch(je, h, ctx->stream, &ctx->last_grid) != 0)
         return OBX_INTERNAL_ERROR;
     } else {
       auto kfn = h.lds_ok
@@ -1144,6 +1224,11 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     }
   }
   HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+  /* table + counters are one allocation: one copy into the pinned buffer,
+     queued before the sync */
+  HIP_TRY(hipMemcpyAsync(ctx->h_result, h.d_gtable,
+                         OBX_RESULT_BYTES(OBX_GTABLE_SLOTS),
+                         hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
@@ -1151,43 +1236,32 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_p0, ctx->ev_p1));
   ctx->last_prep_ms = ms;
 
-  std::vector<gslot> gt(OBX_GTABLE_SLOTS);
+  const gslot *gt = (const gslot *)ctx->h_result;
+  size_t n_gt = OBX_GTABLE_SLOTS;
   unsigned long long cnt[16];
-  HIP_TRY(hipMemcpy(gt.data(), h.d_gtable, sizeof(gslot) * OBX_GTABLE_SLOTS,
-                    hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cnt, h.d_counters, 16 * 8, hipMemcpyDeviceToHost));
+  memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
   if (cnt[1] != 0) {
     /* a workgroup shard overflowed its LDS group table: rerun with the
        direct-global high-cardinality kernel (growth path; AND-only
        filters — OR-programs keep the capacity error) */
     if (ph.n_prog != 0) return OBX_BUF_NOT_ENOUGH;
     if (!h.d_gtable_big)
-      HIP_TRY(hipMalloc(&h.d_gtable_big, sizeof(gslot) * OBX_GTABLE_BIG));
-    std::vector<gslot> init(OBX_GTABLE_BIG);
-    memset(init.data(), 0, sizeof(gslot) * OBX_GTABLE_BIG);
-    for (auto &s2 : init) {
-      s2.key = OBX_KEY_EMPTY;
-      for (uint32_t a = 0; a < ph.n_aggs; a++) {
-        if (ph.aggs[a].kind == OBX_AGG_MIN)
-          s2.cells[a][0] = (unsigned long long)INT64_MAX;
-        else if (ph.aggs[a].kind == OBX_AGG_MAX)
-          s2.cells[a][0] = (unsigned long long)INT64_MIN;
-      }
-    }
-    HIP_TRY(hipMemcpyAsync(h.d_gtable_big, init.data(),
-                           sizeof(gslot) * OBX_GTABLE_BIG,
-                           hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(h.d_counters, 0, 16 * 8, ctx->stream));
+      HIP_TRY(hipMalloc(&h.d_gtable_big, OBX_RESULT_BYTES(OBX_GTABLE_BIG)));
+    /* same layout as the small table: counters behind the slots */
+    unsigned long long *big_counters =
+        (unsigned long long *)(h.d_gtable_big + OBX_GTABLE_BIG);
+    gtable_init(h.d_gtable_big, OBX_GTABLE_BIG, 16, min_mask, max_mask,
+                ctx->stream);
     hipLaunchKernelGGL(k_scan_agg_direct, dim3(grid_for(h.n_blocks)),
                        dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
                        h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
-                       ph, h.d_gtable_big, h.d_counters);
+                       ph, h.d_gtable_big, big_counters);
+    HIP_TRY(hipMemcpyAsync(ctx->h_result, h.d_gtable_big,
+                           OBX_RESULT_BYTES(OBX_GTABLE_BIG),
+                           hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    gt.resize(OBX_GTABLE_BIG);
-    HIP_TRY(hipMemcpy(gt.data(), h.d_gtable_big,
-                      sizeof(gslot) * OBX_GTABLE_BIG,
-                      hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cnt, h.d_counters, 16 * 8, hipMemcpyDeviceToHost));
+    n_gt = OBX_GTABLE_BIG;
+    memcpy(cnt, gt + OBX_GTABLE_BIG, sizeof(cnt));
     if (cnt[2] != 0) return OBX_BUF_NOT_ENOUGH; /* >4096 distinct groups */
   }
   /* slots 8..15: striped per-wave survivor sums */
@@ -1201,8 +1275,8 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     for (int g = 0; g < agg->n_group_cols; g++)
       key_len += h.cols[agg->group_cols[g]].len;
   std::vector<const gslot *> live;
-  for (auto &s : gt)
-    if (s.key != OBX_KEY_EMPTY) live.push_back(&s);
+  for (size_t i = 0; i < n_gt; i++)
+    if (gt[i].key != OBX_KEY_EMPTY) live.push_back(&gt[i]);
   std::sort(live.begin(), live.end(), [](const gslot *a, const gslot *b) {
     /* little-endian packed keys -> compare as memcmp on key bytes */
     uint8_t ka[8], kb[8];
@@ -1325,6 +1399,8 @@ int obx_cs_finish_load(obx_gpu_ctx *ctx, obx_handle *h,
     if (db.block_len > h->max_block_len) h->max_block_len = db.block_len;
   }
   h->lds_ok = lds_ok;
+  h->n_cus = ctx->n_cus;
+  summarize_col_classes(*h);
   /* dict payloads live only on the device for CS handles; the persistent
      JIT path requires the host-verified byte-identical dicts, so it is
      simply not taken (col_dict_stable stays false -> v1 JIT / generic
@@ -1333,8 +1409,8 @@ int obx_cs_finish_load(obx_gpu_ctx *ctx, obx_handle *h,
   HIP_TRY(hipMemcpy(h->d_blocks, blocks.data(),
                     sizeof(dev_block) * blocks.size(),
                     hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->d_counters, 16 * sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc(&h->d_gtable, sizeof(gslot) * OBX_GTABLE_SLOTS));
+  HIP_TRY(hipMalloc(&h->d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS)));
+  h->d_counters = (unsigned long long *)(h->d_gtable + OBX_GTABLE_SLOTS);
   HIP_TRY(hipMalloc(&h->d_pleaves, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES));
   {
     uint64_t nmm = (uint64_t)h->n_blocks * n_cols * 2;
@@ -1377,18 +1453,23 @@ int obx_cs_publish_handle(obx_gpu_ctx *ctx, obx_handle *h) {
  * container has no device; tests hipcc-compile the dump offline).
  * col_flags bits: 1 = dict-everywhere, 2 = ext-any, 4 = bounds known.
  * Returns the source length (>= 0) or a negative status; 0 = the plan
- * would not take the JIT path. */
-extern "C" int64_t obx_jit_dump_src(
+ * would not take the JIT path. The _ex form also takes the block count and
+ * the device's CU count (0 = default), which size the launch grid and with
+ * it the i64 accumulator bound; a v2 source reports that grid in
+ * *grid_out. */
+extern "C" int64_t obx_jit_dump_src_ex(
     const obx_filter_desc *filter, const obx_agg_desc *agg,
     const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_flags,
     const int64_t *col_min, const int64_t *col_max,
     const uint32_t *col_maxcnt, const uint32_t *col_maxw,
-    uint32_t max_block_rows, int force_v1,
-    char *out, int64_t cap) {
+    uint32_t max_block_rows, int force_v1, uint32_t n_blocks, uint32_t n_cus,
+    uint32_t *grid_out, char *out, int64_t cap) {
   if (!cols || n_cols > OBX_DEV_MAX_COLS) return OBX_INVALID_ARGUMENT;
+  if (grid_out) *grid_out = 0;
   obx_handle h;
   h.n_cols = n_cols;
-  h.n_blocks = 1;
+  h.n_blocks = n_blocks ? n_blocks : 1;
+  if (n_cus) h.n_cus = n_cus;
   h.lds_ok = true;
   h.max_block_rows = max_block_rows ? max_block_rows : 4096;
   h.max_block_len = OBX_LDS_STAGE_BYTES - 32;
@@ -1413,6 +1494,7 @@ extern "C" int64_t obx_jit_dump_src(
     h.col_cnt.push_back(
         (uint8_t)(h.col_maxcnt[c] > 254 ? 255 : h.col_maxcnt[c]));
   }
+  summarize_col_classes(h); /* one synthetic block stands for all */
   dev_plan_hdr ph;
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
   int rc = build_plan(h, filter, agg, ph, pl);
@@ -1437,6 +1519,8 @@ extern "C" int64_t obx_jit_dump_src(
   jit_strategy st;
   if (!force_v1) jit_build_strategy(h, ph, js, pl, st);
   if (!st.ok && js.has_mm) return 0; /* v1 cannot do MIN/MAX */
+  if (st.ok && grid_out)
+    *grid_out = jit_grid_for(h.n_blocks, h.n_cus, st.wpb);
   std::string src = st.ok ? jit_gen_source_v2(ph, js, st)
                           : jit_gen_source(ph, js);
   if (out && cap > (int64_t)src.size()) {
@@ -1444,6 +1528,45 @@ extern "C" int64_t obx_jit_dump_src(
     out[src.size()] = 0;
   }
   return (int64_t)src.size();
+}
+
+extern "C" int64_t obx_jit_dump_src(
+    const obx_filter_desc *filter, const obx_agg_desc *agg,
+    const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_flags,
+    const int64_t *col_min, const int64_t *col_max,
+    const uint32_t *col_maxcnt, const uint32_t *col_maxw,
+    uint32_t max_block_rows, int force_v1,
+    char *out, int64_t cap) {
+  return obx_jit_dump_src_ex(filter, agg, cols, n_cols, col_flags, col_min,
+                             col_max, col_maxcnt, col_maxw, max_block_rows,
+                             force_v1, 1, 0, nullptr, out, cap);
+}
+
+/* Debug/test-only: the plan and JIT-eligibility decisions for synthetic
+ * per-(block,col) class / dict-count arrays (n_blocks x n_cols, the layout
+ * of obx_handle::col_class / col_cnt), without a GPU. Returns build_plan's
+ * status when it is not OBX_SUCCESS, else 1 if the plan passes
+ * jit_plan_shape + jit_blocks_ok and 0 if not. */
+extern "C" int obx_jit_probe_blocks(
+    const obx_filter_desc *filter, const obx_agg_desc *agg,
+    const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_class,
+    const uint8_t *col_cnt, uint32_t n_blocks) {
+  if (!cols || !col_class || !col_cnt || n_cols > OBX_DEV_MAX_COLS)
+    return OBX_INVALID_ARGUMENT;
+  obx_handle h;
+  h.n_cols = n_cols;
+  h.n_blocks = n_blocks;
+  h.lds_ok = true;
+  memcpy(h.cols, cols, sizeof(obx_col_schema) * n_cols);
+  h.col_class.assign(col_class, col_class + (size_t)n_blocks * n_cols);
+  h.col_cnt.assign(col_cnt, col_cnt + (size_t)n_blocks * n_cols);
+  summarize_col_classes(h);
+  dev_plan_hdr ph;
+  dev_leaf pl[OBX_DEV_MAX_LEAVES];
+  int rc = build_plan(h, filter, agg, ph, pl);
+  if (rc != OBX_SUCCESS) return rc;
+  jit_shape js;
+  return jit_plan_shape(ph, js) && jit_blocks_ok(h, ph, js) ? 1 : 0;
 }
 
 extern "C" double obx_gpu_last_kernel_ms(obx_gpu_ctx *ctx) {
@@ -1459,6 +1582,11 @@ extern "C" double obx_gpu_last_prep_ms(obx_gpu_ctx *ctx) {
 
 extern "C" int obx_gpu_last_jit(obx_gpu_ctx *ctx) {
   return ctx ? ctx->last_jit : 0;
+}
+
+/* launch grid of the last scan's specialized kernel (0 = generic kernels) */
+extern "C" uint32_t obx_gpu_last_grid(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->last_grid : 0;
 }
 
 extern "C" uint64_t obx_gpu_total_rows(obx_gpu_ctx *ctx, int handle) {

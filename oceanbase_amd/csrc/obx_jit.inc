@@ -37,6 +37,7 @@ static const char *OBX_JIT_SRC_COMMON_H =
 struct jit_entry {
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;
+  int wpb = 0; /* v2: workgroups per CU the launch grid is sized to */
 };
 
 static std::map<std::string, jit_entry> g_jit_cache;
@@ -95,31 +96,48 @@ static bool jit_plan_shape(const dev_plan_hdr &ph, jit_shape &js) {
   return js.n_wa <= 8;
 }
 
-/* per-block eligibility over the whole handle (host-side: the encodings
-   were captured at load time; the JIT kernel then assumes every block is
-   fast — no in-kernel plan machinery, which is the whole point) */
+/* largest per-block group-cell product of a two-column grouping: walked
+   once per (handle, column pair), then served from the handle */
+static uint32_t jit_pair_cells_max(const obx_handle &h, uint8_t c0,
+                                   uint8_t c1) {
+  const uint32_t key = ((uint32_t)c0 << 16) | c1;
+  auto it = h.pair_cells_max.find(key);
+  if (it != h.pair_cells_max.end()) return it->second;
+  const uint32_t nc = h.n_cols;
+  uint32_t mx = 0;
+  for (uint32_t b = 0; b < h.n_blocks; b++) {
+    const uint8_t *cnt = &h.col_cnt[(size_t)b * nc];
+    uint32_t cells = ((uint32_t)cnt[c0] + 1) * ((uint32_t)cnt[c1] + 1);
+    if (cells > mx) mx = cells;
+  }
+  h.pair_cells_max[key] = mx;
+  return mx;
+}
+
+/* eligibility over the whole handle (host-side: the encodings were
+   captured at load time; the JIT kernel then assumes every block is fast —
+   no in-kernel plan machinery, which is the whole point). Reads the
+   per-column folds of the per-block arrays (summarize_col_classes); the
+   decisions are those of a walk over every block: group columns dict with
+   count < 16 and at most 16 cells per block, value columns neither slow
+   nor string. */
 static bool jit_blocks_ok(const obx_handle &h, const dev_plan_hdr &ph,
                           const jit_shape &js) {
   if (!h.lds_ok || h.col_class.empty()) return false;
   uint8_t gcol[2] = {0xFF, 0xFF};
-  for (uint32_t g = 0; g < ph.n_group_cols; g++)
+  uint32_t cells = 1; /* product of the column maxima: an upper bound */
+  for (uint32_t g = 0; g < ph.n_group_cols; g++) {
     gcol[g] = ph.need_cols[ph.group_idx[g]];
-  const uint32_t nc = h.n_cols;
-  for (uint32_t b = 0; b < h.n_blocks; b++) {
-    const uint8_t *cls = &h.col_class[(size_t)b * nc];
-    const uint8_t *cnt = &h.col_cnt[(size_t)b * nc];
-    uint32_t cells = 1;
-    for (uint32_t g = 0; g < ph.n_group_cols; g++) {
-      if ((cls[gcol[g]] & 0xF) != 1) return false; /* group must be dict */
-      if (cnt[gcol[g]] >= 16) return false;
-      cells *= (uint32_t)cnt[gcol[g]] + 1;
-    }
-    if (cells > 16) return false;
-    for (int j = 0; j < js.n_vc; j++) {
-      uint8_t c = cls[js.vcol[j]];
-      if ((c & 0xF) > 3 || (c & 0x10)) return false; /* slow or string */
-    }
+    if (!h.col_grp16_every[gcol[g]]) return false;
+    cells *= h.col_cnt_max[gcol[g]] + 1;
   }
+  /* the maxima may sit in different blocks: only then is the bound loose,
+     and the exact per-block maximum decides */
+  if (cells > 16 && (ph.n_group_cols < 2 ||
+                     jit_pair_cells_max(h, gcol[0], gcol[1]) > 16))
+    return false;
+  for (int j = 0; j < js.n_vc; j++)
+    if (h.col_slow_any[js.vcol[j]]) return false;
   return true;
 }
 
@@ -670,6 +688,7 @@ static jit_entry *jit_get(const dev_plan_hdr &ph, const jit_shape &js,
   if (it != g_jit_cache.end())
     return it->second.fn ? &it->second : nullptr;
   jit_entry ent; /* cache negative results too */
+  ent.wpb = st.ok ? st.wpb : 0;
   g_jit_kind = st.ok ? 2 : 1;
   std::string src = st.ok ? jit_gen_source_v2(ph, js, st)
                           : jit_gen_source(ph, js);
@@ -732,8 +751,15 @@ static jit_entry *jit_prepare(const obx_handle &h, const dev_plan_hdr &ph,
   return jit_get(ph, js, st);
 }
 
-static int jit_launch(jit_entry *je, obx_handle &h, uint32_t grid,
-                      hipStream_t stream) {
+static int jit_launch(jit_entry *je, obx_handle &h, hipStream_t stream,
+                      uint32_t *grid_out) {
+  /* v2 keeps its accumulators for the kernel's lifetime and flushes once
+     per workgroup: its grid is a multiple of the resident set (the grid
+     the strategy proved its i64 bound for); v1 merges per block and keeps
+     the fixed grid */
+  const uint32_t grid = je->wpb ? jit_grid_for(h.n_blocks, h.n_cus, je->wpb)
+                                : grid_for(h.n_blocks);
+  *grid_out = grid;
   void *args[7] = {&h.d_buf,     &h.d_blocks, &h.n_blocks, &h.d_pleaves,
                    &h.d_bleaves, &h.d_gtable, &h.d_counters};
   return hipModuleLaunchKernel(je->fn, grid, 1, 1, OBX_WG_HOST, 1, 1, 0,

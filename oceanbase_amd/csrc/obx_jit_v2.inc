@@ -14,6 +14,15 @@
  *     de-phasing: no convoy exists), OBX_JIT_FPROBE (perf probes),
  *     OBX_JIT_JWS=2 (two-axis fold: occupancy step).
  *
+ * After round 2 (profiles/r03_q1_flush.md), all measured wins and on by
+ * default: the flush reduces per (cell, aggregate) inside the workgroup
+ * before any global atomic; the launch grid is 8x the resident set
+ * (jit_grid_for, obx_engine.cpp — also the grid of the i64 window bound);
+ * packed streams with r * width <= 32 are extracted with 32-bit ops
+ * (OBX_JIT_M32=0 restores the 64-bit reads); a PROD3 term whose operands
+ * are proven to fit multiplies once against a combined u32 factor table
+ * (OBX_JIT_CTAB=0 restores the two-table product).
+ *
  * Round-1 PMC profiling showed the specialized kernel ISSUE-bound: the
  * per-row cost was dominated by the exact-int128 digit-split LDS atomics
  * (4 atomics + guards per aggregate per row) and per-row dict-entry
@@ -109,6 +118,11 @@ struct jit_strategy {
   uint8_t leaf_multi[8] = {}; /* r entries per packed read */
   uint8_t g_multi[2] = {};
   uint8_t v_multi[4] = {};
+  /* ... and that read fits 32 bits (r * max_width <= 32): one
+     v_alignbit_b32 over two dwords, 32-bit shifts and masks per field */
+  uint8_t leaf_m32[8] = {};
+  uint8_t g_m32[2] = {};
+  uint8_t v_m32[4] = {};
   int8_t cnt_hist = -1;      /* cell counts derived from this hist (drops
                                 the per-row wcnt atomic) */
   uint32_t jcells = 16;      /* group-cell rows actually possible */
@@ -125,6 +139,13 @@ struct jit_strategy {
   uint8_t jws_member[OBX_DEV_MAX_AGGS] = {};
   int8_t jws_f0[OBX_DEV_MAX_AGGS];          /* flush factor tab / axis0 */
   int8_t jws_f1[OBX_DEV_MAX_AGGS];          /* flush factor tab / axis1 */
+  /* narrowed PROD3: when the weight is a CTX column proven in [0, 2^32)
+     and both dict factors are proven non-negative with a product below
+     2^32, the per-row term is ONE u32 x u32 -> u64 multiply against a
+     combined LDS table vtc[xb][xc] = (one_b - eb) * (one_c + ec), instead
+     of two 64 x 64 multiplies over two table reads */
+  int8_t ctab_agg = -1;
+  uint32_t ctab_db = 0, ctab_dc = 0;
   uint32_t lds_bytes = 0;
   int wpb = 7;
 };
@@ -197,12 +218,10 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     if (!st.leaf_inline)
       for (uint32_t i = 0; i < 8; i++) st.leaf_kind[i] = 0;
   }
-  /* i64 accumulators persist across every block a workgroup scans */
-  uint32_t grid = h.n_blocks < 4096u ? h.n_blocks : 4096u;
-  if (grid == 0) grid = 1;
-  const uint64_t maxrows =
-      (uint64_t)((h.n_blocks + grid - 1) / grid) *
-      (h.max_block_rows ? h.max_block_rows : 4096);
+  /* i64 accumulators persist across every block a workgroup scans, so
+     their safety bound needs the launch grid, and that needs wpb: the
+     largest |term| is collected here and tested once wpb is known (end) */
+  uint64_t max_term = 0;
   const uint64_t BOUND = 1ull << 62;
 
   /* group-cell count: per-cell LDS arrays are sized to the real
@@ -280,7 +299,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
           st.ahist[a] = (int8_t)hid;
         } else {
           if (!maxabs_of(g.ia, &ma)) return false;
-          if (jit_sat_mul(ma, maxrows) >= BOUND) return false;
+          if (ma > max_term) max_term = ma;
           st.astrat[a] = JA_I64;
           st.wa64[a] = (int8_t)st.n_w64++;
           st.aval_a[a] = (int8_t)ja;
@@ -303,7 +322,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
             term = jit_sat_mul(term, onec + mc);
           }
         }
-        if (jit_sat_mul(term, maxrows) >= BOUND) return false;
+        if (term > max_term) max_term = term;
         st.astrat[a] = JA_I64;
         st.wa64[a] = (int8_t)st.n_w64++;
         st.aval_a[a] = (int8_t)ja;
@@ -499,6 +518,45 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     }
   }
 
+  /* product narrowing (first eligible PROD3 that kept its window slot) */
+  {
+    const char *ce = getenv("OBX_JIT_CTAB");
+    const bool allow = !ce || ce[0] != '0';
+    for (uint32_t a = 0; allow && a < ph.n_aggs && st.ctab_agg < 0; a++) {
+      const dev_agg &g = ph.aggs[a];
+      if (g.kind != OBX_AGG_SUM_PROD3 || st.astrat[a] != JA_I64 ||
+          st.jws_member[a] || st.wa64[a] < 0 || st.atab_a[a] >= 0 ||
+          st.atab_b[a] < 0 || st.atab_c[a] < 0)
+        continue;
+      /* the PROD2 head, when it runs per row, shares p2 with this agg */
+      if (a > 0 && (js.agg_f2 & (1u << (a - 1))) && !st.jws_member[a - 1])
+        continue;
+      const uint16_t ca = ph.need_cols[g.ia], cb = ph.need_cols[g.ib],
+                     cc = ph.need_cols[g.ic];
+      if (!h.col_known[ca] || !h.col_known[cb] || !h.col_known[cc]) continue;
+      const bool empty_b = h.col_min[cb] > h.col_max[cb],
+                 empty_c = h.col_min[cc] > h.col_max[cc];
+      if (h.col_min[ca] > h.col_max[ca] || empty_b || empty_c) continue;
+      if (h.col_min[ca] < 0 || h.col_max[ca] > (int64_t)0xffffffffll)
+        continue;
+      /* factor ranges over every dict entry (the stored bounds of a dict
+         column cover its whole dict): one_b - e and one_c + e */
+      const __int128 fb_lo = (__int128)g.one_b - h.col_max[cb],
+                     fb_hi = (__int128)g.one_b - h.col_min[cb],
+                     fc_lo = (__int128)g.one_c + h.col_min[cc],
+                     fc_hi = (__int128)g.one_c + h.col_max[cc];
+      if (fb_lo < 0 || fc_lo < 0 || fb_hi > 0xffffffffll ||
+          fc_hi > 0xffffffffll || fb_hi * fc_hi > 0xffffffffll)
+        continue;
+      const uint32_t db = st.tabs[st.atab_b[a]].dim,
+                     dc = st.tabs[st.atab_c[a]].dim;
+      if ((uint64_t)db * dc > 1024) continue;
+      st.ctab_agg = (int8_t)a;
+      st.ctab_db = db;
+      st.ctab_dc = dc;
+    }
+  }
+
   /* strip mining: r rows per lane when the filter is inline (or absent);
      a packed stream is read r-entries-at-once when r * max_width <= 64 */
   if (st.leaf_inline || ph.n_leaves == 0) {
@@ -507,17 +565,24 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     if (r != 1 && r != 2 && r != 4 && r != 8) r = 4;
     st.r = (uint8_t)r;
     if (st.r > 1) {
-      for (uint32_t i = 0; i < ph.n_leaves; i++)
-        st.leaf_multi[i] =
-            h.col_maxw[st.leaf_cols[i]] * st.r <= 64 ? 1 : 0;
-      for (uint32_t g2 = 0; g2 < ph.n_group_cols; g2++)
-        st.g_multi[g2] =
-            h.col_maxw[ph.need_cols[ph.group_idx[g2]]] * st.r <= 64 ? 1 : 0;
-      for (int j = 0; j < js.n_vc; j++)
-        st.v_multi[j] = (st.vmode[j] == JV_REF &&
-                         h.col_maxw[js.vcol[j]] * st.r <= 64)
-                            ? 1
-                            : 0;
+      const char *ne = getenv("OBX_JIT_M32");
+      const uint32_t w32 = (ne && ne[0] == '0') ? 0 : 32;
+      for (uint32_t i = 0; i < ph.n_leaves; i++) {
+        const uint32_t rw = h.col_maxw[st.leaf_cols[i]] * st.r;
+        st.leaf_multi[i] = rw <= 64 ? 1 : 0;
+        st.leaf_m32[i] = rw <= w32 ? 1 : 0;
+      }
+      for (uint32_t g2 = 0; g2 < ph.n_group_cols; g2++) {
+        const uint32_t rw =
+            h.col_maxw[ph.need_cols[ph.group_idx[g2]]] * st.r;
+        st.g_multi[g2] = rw <= 64 ? 1 : 0;
+        st.g_m32[g2] = rw <= w32 ? 1 : 0;
+      }
+      for (int j = 0; j < js.n_vc; j++) {
+        const uint32_t rw = h.col_maxw[js.vcol[j]] * st.r;
+        st.v_multi[j] = (st.vmode[j] == JV_REF && rw <= 64) ? 1 : 0;
+        st.v_m32[j] = (st.vmode[j] == JV_REF && rw <= w32) ? 1 : 0;
+      }
     }
   }
   /* any full histogram records every live row (nulls in the clamp
@@ -542,6 +607,10 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   st.stage_bytes = ((h.max_block_len + 24 + 63) / 64) * 64;
   if (st.stage_bytes > OBX_LDS_STAGE_BYTES + 32)
     st.stage_bytes = OBX_LDS_STAGE_BYTES + 32;
+  /* the flush reuses the stage buffer for its per-(cell, aggregate)
+     partials (16 B each): tiny blocks must not undersize it */
+  if (st.stage_bytes < st.jcells * ph.n_aggs * 16)
+    st.stage_bytes = ((st.jcells * ph.n_aggs * 16 + 63) / 64) * 64;
   /* (a double-buffered stage was tried and reverted: 2x stage LDS
      halves occupancy, which outweighs the DMA overlap, and the LDS-DMA
      destination must stay uniform+lane-linear) */
@@ -556,6 +625,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   lds += (uint32_t)st.n_mm * st.jcells * 16; /* wmm val + valid */
   lds += st.hist_total * 4;                      /* histograms */
   for (int t = 0; t < st.n_tab; t++) lds += st.tabs[t].dim * 8;
+  if (st.ctab_agg >= 0) lds += st.ctab_db * st.ctab_dc * 4;
   lds += 16 * 8 + 16 * 4;                        /* keytab + cslot */
   if (st.jws_on)
     lds += st.jws_cells * st.jws_d0 * st.jws_d1 * 8; /* joint wsum */
@@ -570,6 +640,15 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     if (w >= 2 && w <= 8 && w < st.wpb) st.wpb = w;
   }
   if (st.wpb < 2) return false;
+  /* i64 window bound over the rows one workgroup sweeps at the launched
+     grid (jit_grid_for is what jit_launch uses) */
+  {
+    const uint32_t grid = jit_grid_for(h.n_blocks, h.n_cus, st.wpb);
+    const uint64_t maxrows =
+        (uint64_t)((h.n_blocks + grid - 1) / grid) *
+        (h.max_block_rows ? h.max_block_rows : 4096);
+    if (jit_sat_mul(max_term, maxrows) >= BOUND) return false;
+  }
   st.ok = true;
   return true;
 }
@@ -583,8 +662,10 @@ static std::string jit_strategy_sig(const jit_strategy &st) {
            st.sdb + 10 * st.skew, st.n_mm);
   k += b;
   for (int i = 0; i < 8; i++) {
-    snprintf(b, sizeof b, "m%d%d%d|", i < 8 ? st.leaf_multi[i] : 0,
-             i < 2 ? st.g_multi[i] : 0, i < 4 ? st.v_multi[i] : 0);
+    snprintf(b, sizeof b, "m%d%d%d|",
+             i < 8 ? st.leaf_multi[i] + 2 * st.leaf_m32[i] : 0,
+             i < 2 ? st.g_multi[i] + 2 * st.g_m32[i] : 0,
+             i < 4 ? st.v_multi[i] + 2 * st.v_m32[i] : 0);
     k += b;
   }
   for (int i = 0; i < 8; i++) {
@@ -607,6 +688,8 @@ static std::string jit_strategy_sig(const jit_strategy &st) {
              (long long)st.tabs[t].one, st.tabs[t].dim);
     k += b;
   }
+  snprintf(b, sizeof b, "C%d:%u:%u|", st.ctab_agg, st.ctab_db, st.ctab_dc);
+  k += b;
   if (st.jws_on) {
     snprintf(b, sizeof b, "J%d:%d:%d:%u:%u:%u|", st.jws_ja, st.jws_a0,
              st.jws_a1, st.jws_d0, st.jws_d1, st.jws_cells);
@@ -666,6 +749,15 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "  if (k < 64) v &= (((uint64_t)1 << k) - 1);\n"
        "  return v;\n"
        "}\n"
+       "/* the 32 bits at bitpos from a 4-B-aligned base (callers mask\n"
+       "   their fields out of it) */\n"
+       "__device__ __forceinline__ uint32_t jit_bread32(\n"
+       "    const uint8_t *__restrict__ b, uint32_t bitpos) {\n"
+       "  const uint32_t *w = (const uint32_t *)b;\n"
+       "  const uint32_t widx = bitpos >> 5;\n"
+       "  return __builtin_amdgcn_alignbit(w[widx + 1], w[widx], bitpos & "
+       "31);\n"
+       "}\n"
       "__device__ __forceinline__ int jit_gslot(gslot *gt, uint64_t key) {\n"
       "  uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - OBX_GTABLE_SHIFT)) &\n"
       "                 (OBX_GTABLE_SLOTS - 1);\n"
@@ -698,9 +790,11 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   s += b;
   const int sdb = st.sdb ? 1 : 0;
   if (sdb)
-    s += "  __shared__ uint8_t sega[JSTAGE], segb[JSTAGE];\n";
+    s += "  __shared__ __attribute__((aligned(16))) uint8_t sega[JSTAGE],\n"
+         "      segb[JSTAGE];\n";
   else
-    s += "  __shared__ uint8_t lds_blk[JSTAGE];\n";
+    s += "  __shared__ __attribute__((aligned(16))) uint8_t "
+         "lds_blk[JSTAGE];\n";
   s += ""
        "  __shared__ unsigned long long wacc64[NW64][JC][NSTRIPE];\n"
        "  __shared__ uint32_t hist[HTOT];\n";
@@ -725,6 +819,13 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   for (int t = 0; t < st.n_tab; t++) {
     snprintf(b, sizeof b, "  __shared__ long long vt%d[%u];\n", t,
              st.tabs[t].dim);
+    s += b;
+  }
+  if (st.ctab_agg >= 0) {
+    snprintf(b, sizeof b,
+             "  /* combined factor table [xb][xc] of the narrowed PROD3 */\n"
+             "  __shared__ uint32_t vtc[%uu * %uu];\n",
+             st.ctab_db, st.ctab_dc);
     s += b;
   }
   s += "  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> "
@@ -791,6 +892,26 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "      }\n"
              "    }\n",
              (unsigned)js.vcol[st.tabs[t].vc], st.tabs[t].dim, ex, t);
+    s += b;
+  }
+  if (st.ctab_agg >= 0) {
+    const dev_agg &g = ph.aggs[st.ctab_agg];
+    snprintf(b, sizeof b,
+             "    {\n"
+             "      const dev_col *tb = &b0.cols[%u], *tc = &b0.cols[%u];\n"
+             "      for (uint32_t e = tid; e < %uu * %uu; e += WG) {\n"
+             "        const uint32_t eb = e / %uu, ec = e %% %uu;\n"
+             "        long long fb = 0, fc = 0; /* null slots: factor 0 */\n"
+             "        if (eb < tb->count) fb = %lldll - dict_entry(bv0, *tb, "
+             "eb);\n"
+             "        if (ec < tc->count) fc = %lldll + dict_entry(bv0, *tc, "
+             "ec);\n"
+             "        vtc[e] = (uint32_t)(fb * fc);\n"
+             "      }\n"
+             "    }\n",
+             (unsigned)ph.need_cols[g.ib], (unsigned)ph.need_cols[g.ic],
+             st.ctab_db, st.ctab_dc, st.ctab_dc, st.ctab_dc,
+             (long long)g.one_b, (long long)g.one_c);
     s += b;
   }
   if (NG > 0) {
@@ -932,20 +1053,30 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
       body += b;
     }
     if (st.r > 1 && st.leaf_multi[i]) {
-      snprintf(b, sizeof b,
-               "    const uint64_t lm%d = (1ull << l%dW) - 1;\n", i, i);
+      if (st.leaf_m32[i])
+        snprintf(b, sizeof b,
+                 "    const uint32_t lm%d = (1u << l%dW) - 1;\n", i, i);
+      else
+        snprintf(b, sizeof b,
+                 "    const uint64_t lm%d = (1ull << l%dW) - 1;\n", i, i);
       body += b;
     }
   }
   if (st.r > 1) {
     if (NG > 0 && st.g_multi[0])
-      body += "    const uint64_t gm0 = (1ull << gW0) - 1;\n";
+      body += st.g_m32[0] ? "    const uint32_t gm0 = (1u << gW0) - 1;\n"
+                          : "    const uint64_t gm0 = (1ull << gW0) - 1;\n";
     if (NG > 1 && st.g_multi[1])
-      body += "    const uint64_t gm1 = (1ull << gW1) - 1;\n";
+      body += st.g_m32[1] ? "    const uint32_t gm1 = (1u << gW1) - 1;\n"
+                          : "    const uint64_t gm1 = (1ull << gW1) - 1;\n";
     for (int j = 0; j < js.n_vc; j++)
       if (st.v_multi[j]) {
-        snprintf(b, sizeof b,
-                 "    const uint64_t xm%d = (1ull << xW%d) - 1;\n", j, j);
+        if (st.v_m32[j])
+          snprintf(b, sizeof b,
+                   "    const uint32_t xm%d = (1u << xW%d) - 1;\n", j, j);
+        else
+          snprintf(b, sizeof b,
+                   "    const uint64_t xm%d = (1ull << xW%d) - 1;\n", j, j);
         body += b;
       }
   }
@@ -1081,6 +1212,16 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
             !st.jws_member[a - 1])
           break;
         int jb = slot_lookup(g.ib), jc = slot_lookup(g.ic);
+        if (st.ctab_agg == (int)a) {
+          snprintf(b, sizeof b,
+                   "          atomicAdd(&wacc64[%d][cell][stripe],\n"
+                   "                    (unsigned long long)(uint32_t)v%d *\n"
+                   "                        (unsigned long long)vtc[x%d * %uu "
+                   "+ x%d]);\n",
+                   st.wa64[a], ja, jb, st.ctab_dc, jc);
+          acc += b;
+          break;
+        }
         char vb[64], vc[64];
         if (st.atab_b[a] >= 0)
           snprintf(vb, sizeof vb, "vt%d[x%d]", st.atab_b[a], jb);
@@ -1116,32 +1257,44 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   sweep2 += b;
   for (int i = 0; i < NL; i++)
     if (st.leaf_multi[i]) {
-      snprintf(b, sizeof b,
-               "      uint64_t wl%d = jit_bread(bv.base, l%do + rbase * "
-               "l%dW, %d * l%dW);\n",
-               i, i, i, R, i);
+      if (st.leaf_m32[i])
+        snprintf(b, sizeof b,
+                 "      uint32_t wl%d = jit_bread32(bv.base, l%do + rbase * "
+                 "l%dW);\n",
+                 i, i, i);
+      else
+        snprintf(b, sizeof b,
+                 "      uint64_t wl%d = jit_bread(bv.base, l%do + rbase * "
+                 "l%dW, %d * l%dW);\n",
+                 i, i, i, R, i);
       sweep2 += b;
     }
-  if (NG > 0 && st.g_multi[0]) {
-    snprintf(b, sizeof b,
-             "      uint64_t wgr0 = jit_bread(bv.base, go0 + rbase * gW0, "
-             "%d * gW0);\n",
-             R);
-    sweep2 += b;
-  }
-  if (NG > 1 && st.g_multi[1]) {
-    snprintf(b, sizeof b,
-             "      uint64_t wgr1 = jit_bread(bv.base, go1 + rbase * gW1, "
-             "%d * gW1);\n",
-             R);
+  for (int g2 = 0; g2 < NG && g2 < 2; g2++) {
+    if (!st.g_multi[g2]) continue;
+    if (st.g_m32[g2])
+      snprintf(b, sizeof b,
+               "      uint32_t wgr%d = jit_bread32(bv.base, go%d + rbase * "
+               "gW%d);\n",
+               g2, g2, g2);
+    else
+      snprintf(b, sizeof b,
+               "      uint64_t wgr%d = jit_bread(bv.base, go%d + rbase * "
+               "gW%d, %d * gW%d);\n",
+               g2, g2, g2, R, g2);
     sweep2 += b;
   }
   for (int j = 0; j < js.n_vc; j++)
     if (st.v_multi[j]) {
-      snprintf(b, sizeof b,
-               "      uint64_t wx%d = jit_bread(bv.base, xo%d + rbase * "
-               "xW%d, %d * xW%d);\n",
-               j, j, j, R, j);
+      if (st.v_m32[j])
+        snprintf(b, sizeof b,
+                 "      uint32_t wx%d = jit_bread32(bv.base, xo%d + rbase * "
+                 "xW%d);\n",
+                 j, j, j);
+      else
+        snprintf(b, sizeof b,
+                 "      uint64_t wx%d = jit_bread(bv.base, xo%d + rbase * "
+                 "xW%d, %d * xW%d);\n",
+                 j, j, j, R, j);
       sweep2 += b;
     }
   for (int j = 0; j < js.n_vc; j++)
@@ -1377,6 +1530,38 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   } else {
     s += "  const uint32_t fcells = 1;\n";
   }
+  /* Hierarchical flush: everything summed over dict refs or joint-cell
+     slices (passes 2 and 3) is first reduced inside the workgroup, in
+     exact int128 in LDS, so each workgroup sends ONE global accumulate per
+     (cell, aggregate) instead of one per ref -- the per-ref form put ~87
+     same-address L2 atomics per live cell per workgroup on four slots.
+     The partials live in the stage buffer, which is idle by now. */
+  uint32_t f_sum = 0, f_min = 0, f_max = 0; /* aggregates going via facc */
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (st.astrat[a] == JA_HIST || st.astrat[a] == JA_HCOUNT ||
+        (st.jws_on && st.jws_member[a]))
+      f_sum |= 1u << a;
+    else if (st.astrat[a] == JA_HISTMM)
+      (ph.aggs[a].kind == OBX_AGG_MIN ? f_min : f_max) |= 1u << a;
+  }
+  const bool f_any = (f_sum | f_min | f_max) != 0;
+  if (f_any) {
+    snprintf(b, sizeof b,
+             "  /* workgroup partials [cell][agg]: {lo, hi} of an int128\n"
+             "     sum, or {value, valid} of a min/max */\n"
+             "  unsigned long long (*facc)[NAGGS][2] =\n"
+             "      (unsigned long long (*)[NAGGS][2])%s;\n"
+             "  for (uint32_t i = tid; i < JC * NAGGS; i += WG) {\n"
+             "    const uint32_t a = i %% NAGGS;\n"
+             "    facc[i / NAGGS][a][0] =\n"
+             "        ((0x%xu >> a) & 1)   ? (unsigned long long)INT64_MAX\n"
+             "        : ((0x%xu >> a) & 1) ? (unsigned long long)INT64_MIN\n"
+             "                             : 0ull;\n"
+             "    facc[i / NAGGS][a][1] = 0;\n"
+             "  }\n",
+             sdb ? "sega" : "lds_blk", f_min, f_max);
+    s += b;
+  }
   s += "  /* flush pass 1: per-cell counts, keys -> global slots */\n"
        "  for (uint32_t cell = tid; cell < fcells; cell += WG) {\n"
        "    int ce = -1;\n";
@@ -1480,9 +1665,10 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
         snprintf(b, sizeof b,
                  "      {\n"
                  "        __int128 p = (__int128)ev * (long long)c2;\n"
-                 "        g_acc_i128(gtable[ce].cells[%u], (uint64_t)p,\n"
-                 "                   (uint64_t)((unsigned __int128)p >> "
-                 "64));\n"
+                 "        i128v pv = {(uint64_t)p,\n"
+                 "                    (uint64_t)((unsigned __int128)p >> "
+                 "64)};\n"
+                 "        lds_acc_i128(facc[cell][%u], pv);\n"
                  "      }\n",
                  (unsigned)a);
         s += b;
@@ -1490,9 +1676,9 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
         /* any live dict entry bounds the min/max */
         snprintf(b, sizeof b,
                  "      {\n"
-                 "        cas_minmax(&gtable[ce].cells[%u][0],\n"
+                 "        cas_minmax(&facc[cell][%u][0],\n"
                  "                   (int64_t)vt%d[ref], %s);\n"
-                 "        gtable[ce].cells[%u][1] = 1;\n"
+                 "        facc[cell][%u][1] = 1;\n"
                  "      }\n",
                  (unsigned)a, st.atab_a[a],
                  ph.aggs[a].kind == OBX_AGG_MIN ? "true" : "false",
@@ -1500,8 +1686,8 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
         s += b;
       } else { /* JA_HCOUNT */
         snprintf(b, sizeof b,
-                 "      g_acc_i128(gtable[ce].cells[%u], (uint64_t)c2, "
-                 "0);\n",
+                 "      atomicAdd(&facc[cell][%u][0], (unsigned long "
+                 "long)c2);\n",
                  (unsigned)a);
         s += b;
       }
@@ -1572,16 +1758,40 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
       snprintf(b, sizeof b,
                "      {\n"
                "        __int128 p = %s;\n"
-               "        if (p != 0)\n"
-               "          g_acc_i128(gtable[ce].cells[%u], (uint64_t)p,\n"
-               "                     (uint64_t)((unsigned __int128)p >> "
-               "64));\n"
+               "        if (p != 0) {\n"
+               "          i128v pv = {(uint64_t)p,\n"
+               "                      (uint64_t)((unsigned __int128)p >> "
+               "64)};\n"
+               "          lds_acc_i128(facc[cell][%u], pv);\n"
+               "        }\n"
                "      }\n",
                expr, (unsigned)a);
       s += b;
     }
     s += "    }\n"
          "  }\n";
+  }
+  if (f_any) {
+    snprintf(b, sizeof b,
+             "  __syncthreads();\n"
+             "  /* flush pass 4: one global accumulate per (cell, aggregate) "
+             "*/\n"
+             "  for (uint32_t idx = tid; idx < fcells * NAGGS; idx += WG) {\n"
+             "    const uint32_t cell = idx / NAGGS, a = idx %% NAGGS;\n"
+             "    const int ce = cslot[cell];\n"
+             "    if (ce < 0) continue;\n"
+             "    const unsigned long long lo = facc[cell][a][0],\n"
+             "                             hi = facc[cell][a][1];\n"
+             "    if ((0x%xu >> a) & 1) {\n"
+             "      if (lo | hi) g_acc_i128(gtable[ce].cells[a], lo, hi);\n"
+             "    } else if (((0x%xu >> a) & 1) && hi) {\n"
+             "      cas_minmax(&gtable[ce].cells[a][0], (int64_t)lo,\n"
+             "                 (0x%xu >> a) & 1);\n"
+             "      gtable[ce].cells[a][1] = 1;\n"
+             "    }\n"
+             "  }\n",
+             f_sum, f_min | f_max, f_min);
+    s += b;
   }
   s += "}\n";
   return s;

@@ -1072,6 +1072,31 @@ extern "C" __global__ void k_lower_leaves(
   out[idx] = o;
 }
 
+/* Empty group table, written on the device before every scan: one u64 word
+ * per thread over n_slots gslots plus tail_words zeroed counter words that
+ * sit behind the table. Slot layout: key, count, cells[a][4]; MIN/MAX cells
+ * start at their sentinel in limb 0 (bit a of min_mask / max_mask). */
+extern "C" __global__ void k_gtable_init(
+    unsigned long long *__restrict__ words, uint32_t n_slots,
+    uint32_t tail_words, uint32_t min_mask, uint32_t max_mask) {
+  const uint32_t SW = (uint32_t)(sizeof(gslot) / 8);
+  const uint32_t total = n_slots * SW + tail_words;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  unsigned long long v = 0;
+  if (i < n_slots * SW) {
+    const uint32_t w = i % SW;
+    if (w == 0) {
+      v = OBX_KEY_EMPTY;
+    } else if (w >= 2 && ((w - 2) & 3) == 0) {
+      const uint32_t a = (w - 2) >> 2;
+      if ((min_mask >> a) & 1) v = (unsigned long long)INT64_MAX;
+      else if ((max_mask >> a) & 1) v = (unsigned long long)INT64_MIN;
+    }
+  }
+  words[i] = v;
+}
+
 /* Per-(block,column) min/max of the NON-NULL decoded values, captured once
  * at load time — the engine's stored skip index (the reference writes
  * ObSkipIndex min/max rows at encode time, storage/blocksstable/index_block;
