@@ -7,7 +7,8 @@ HIPCC=${HIPCC:-hipcc}
 # embed the device headers for the hipRTC JIT (obx_jit.inc)
 python3 - << 'PYEOF'
 for src, out in (("obx_dev.h", "obx_embed_dev_h.inc"),
-                 ("obx_dev_common.h", "obx_embed_common_h.inc")):
+                 ("obx_dev_common.h", "obx_embed_common_h.inc"),
+                 ("obx_jit_dev.h", "obx_embed_jit_dev_h.inc")):
     txt = open(src).read()
     assert ')OBXRAW"' not in txt
     open(out, "w").write('R"OBXRAW(' + txt + ')OBXRAW"\n')

@@ -261,7 +261,7 @@ static uint32_t grid_for(uint32_t n_blocks) {
   return g ? g : 1;
 }
 
-/* grid of the persistent scan JIT (obx_jit_v2.inc): OBX_JIT_GRID_WAVES
+/* grid of the persistent scan JIT (obx_jit_scan.inc): OBX_JIT_GRID_WAVES
    times what is resident at wpb workgroups per CU, and never more
    workgroups than blocks. Each workgroup flushes once, a handful of global
    atomics per live cell, so the grid is free to be finer than the resident
@@ -979,7 +979,7 @@ extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
   }
   HIP_TRY(hipMemsetAsync(h.d_counters, 0, 16 * 8, ctx->stream));
   /* bitmap-only filters take the specialized wave-per-block kernel
-     (direct global reads of just the leaf streams; obx_jit_v2.inc) */
+     (direct global reads of just the leaf streams; obx_jit_filter.inc) */
   jit_entry *fje = jit_prepare_filter(h, ph, plv, want_row_ids);
   ctx->last_jit = fje ? 2 : 0;
   HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
@@ -1500,7 +1500,7 @@ extern "C" int64_t obx_jit_dump_src_ex(
   int rc = build_plan(h, filter, agg, ph, pl);
   if (rc != OBX_SUCCESS) return rc;
   if (!agg) { /* bitmap-filter path: dump the wave-per-block filter JIT */
-    jit_strategy fst;
+    jit_fstrategy fst;
     if (!jit_build_fstrategy(h, ph, pl, fst)) return 0;
     if (getenv("OBX_DUMP_RID") && fst.fstage) { /* test hook */
       fst.frid = 1;

@@ -1,27 +1,24 @@
 /*
- * obx_jit_v2.inc — second-generation hipRTC query codegen (included by
- * obx_jit.inc).
+ * obx_jit_scan.inc — second-generation (persistent-accumulator) scan
+ * codegen: strategy, strategy signature, source (included by obx_jit.inc).
  *
- * Round-2 note — env knobs and their measured status (profiles/r02_*):
- *   defaults (all measured best):  R=4 strip mining, stripes=4,
- *     single-axis JWS, jcells-sized LDS, striped counter slots,
- *     staged filter (FSTAGE=1) with grid n_blocks/8 in [512,2048].
- *   A/B'd neutral-or-worse, kept env-gated OFF for reproducibility:
- *     OBX_JIT_FDB2 (filter double-buffer: ISA-verified glds span,
- *     measured neutral — strided-stage ceiling), OBX_JIT_FNB (block
- *     batching: LDS vs occupancy), OBX_JIT_SDB (scan 2-phase overlap:
- *     span dies at the sweep's LDS atomics), OBX_JIT_SKEW (convoy
- *     de-phasing: no convoy exists), OBX_JIT_FPROBE (perf probes),
- *     OBX_JIT_JWS=2 (two-axis fold: occupancy step).
+ * Defaults, all measured best (profiles/r02_*, profiles/r03_q1_flush.md):
+ * R=4 strip mining, 4 accumulator stripes, single-axis joint histogram
+ * unless two axes stay under 2 KB, jcells-sized LDS, striped counter slots,
+ * in-workgroup flush reduction, launch grid 8x the resident set
+ * (jit_grid_for, obx_engine.cpp — also the grid of the i64 window bound),
+ * 32-bit extraction of packed streams with r * width <= 32 (OBX_JIT_M32=0
+ * restores the 64-bit reads), one multiply against a combined u32 factor
+ * table for a PROD3 term whose operands are proven to fit (OBX_JIT_CTAB=0
+ * restores the two-table product). OBX_JIT_R, OBX_JIT_STRIPES, OBX_JIT_WPB
+ * and OBX_JIT_JWS=0 override the rest.
  *
- * After round 2 (profiles/r03_q1_flush.md), all measured wins and on by
- * default: the flush reduces per (cell, aggregate) inside the workgroup
- * before any global atomic; the launch grid is 8x the resident set
- * (jit_grid_for, obx_engine.cpp — also the grid of the i64 window bound);
- * packed streams with r * width <= 32 are extracted with 32-bit ops
- * (OBX_JIT_M32=0 restores the 64-bit reads); a PROD3 term whose operands
- * are proven to fit multiplies once against a combined u32 factor table
- * (OBX_JIT_CTAB=0 restores the two-table product).
+ * Experiments that measured neutral or worse are no longer carried here:
+ * the scan's overlapped two-phase block loop, the per-workgroup start
+ * skew and the forced two-axis fold, and the filter kernel's double
+ * buffer, block batching and perf probes. Their measurements are in
+ * profiles/r02_q1.md and profiles/r02_filter_jit.md, under the env knob
+ * names they had; their code is in git at commit 6ddb15c and before.
  *
  * Round-1 PMC profiling showed the specialized kernel ISSUE-bound: the
  * per-row cost was dominated by the exact-int128 digit-split LDS atomics
@@ -105,15 +102,6 @@ struct jit_strategy {
   uint16_t leaf_cols[8] = {};
   uint8_t r = 1;             /* rows per lane (strip mining) */
   uint8_t stripes = 4;       /* i64 accumulator lane stripes */
-  uint8_t fu = 4;            /* filter kernel: pipelined tiles */
-  uint8_t sdb = 0;           /* scan kernel: overlapped 2-phase stage */
-  uint8_t skew = 0;          /* per-WG start skew (us) to break the
-                                stage/sweep convoy across co-resident WGs */
-  uint8_t fprobe = 0;        /* perf probe: 1 no-flush, 2 loads-only */
-  uint8_t fstage = 0;        /* filter: LDS-DMA stage leaf streams */
-  uint8_t frid = 0;          /* filter: emit ordered selection vectors */
-  uint16_t fnch = 64;        /* chunk capacity for the mask capture */
-  uint32_t fseg[4] = {};     /* per-leaf LDS segment bytes (staged mode) */
   uint32_t stage_bytes = OBX_LDS_STAGE_BYTES + 32;
   uint8_t leaf_multi[8] = {}; /* r entries per packed read */
   uint8_t g_multi[2] = {};
@@ -433,10 +421,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         return d ? d : 1;
       };
       const uint32_t cells0 = st.jcells;
-      const char *me = getenv("OBX_JIT_JWS");
-      bool force2 = me && me[0] == '2';
-      if (!force2 &&
-          (uint64_t)cells0 * adim(axes[0]) * adim(axes[1]) * 8 > 2048) {
+      if ((uint64_t)cells0 * adim(axes[0]) * adim(axes[1]) * 8 > 2048) {
         /* count members per axis, keep the busier one */
         int use[2] = {0, 0};
         for (uint32_t a = 0; a < ph.n_aggs; a++) {
@@ -614,13 +599,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   /* (a double-buffered stage was tried and reverted: 2x stage LDS
      halves occupancy, which outweighs the DMA overlap, and the LDS-DMA
      destination must stay uniform+lane-linear) */
-  {
-    const char *sde = getenv("OBX_JIT_SDB");
-    st.sdb = sde && sde[0] == '1' ? 1 : 0;
-    const char *ske = getenv("OBX_JIT_SKEW");
-    st.skew = ske ? (uint8_t)atoi(ske) : 0;
-  }
-  uint32_t lds = st.stage_bytes * (st.sdb ? 2 : 1);
+  uint32_t lds = st.stage_bytes;
   lds += (uint32_t)st.n_w64 * st.jcells * 8 * st.stripes;
   lds += (uint32_t)st.n_mm * st.jcells * 16; /* wmm val + valid */
   lds += st.hist_total * 4;                      /* histograms */
@@ -656,10 +635,9 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
 static std::string jit_strategy_sig(const jit_strategy &st) {
   char b[256];
   std::string k = "V2|";
-  snprintf(b, sizeof b, "w%dh%dt%dp%dli%dr%dch%ds%du%uc%ub%dm%d|",
+  snprintf(b, sizeof b, "w%dh%dt%dp%dli%dr%dch%ds%du%uc%um%d|",
            st.n_w64, st.n_hist, st.n_tab, st.wpb, st.leaf_inline, st.r,
-           st.cnt_hist, st.stripes, st.stage_bytes, st.jcells,
-           st.sdb + 10 * st.skew, st.n_mm);
+           st.cnt_hist, st.stripes, st.stage_bytes, st.jcells, st.n_mm);
   k += b;
   for (int i = 0; i < 8; i++) {
     snprintf(b, sizeof b, "m%d%d%d|",
@@ -710,65 +688,16 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   const int NL = ph.n_leaves;
   char b[1024];
   std::string s;
-  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n\n";
+  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
+       "#include \"obx_jit_dev.h\"\n\n";
   snprintf(b, sizeof b,
            "#define NL %d\n#define NG %d\n#define NW64 %d\n"
            "#define NAGGS %u\n#define HTOT %u\n#define NSTRIPE %u\n"
-           "#define JSTAGE %u\n#define JC %u\n"
-           "#define PW(dc)                                              \\\n"
-           "  (((dc).flags & OBX_DF_BITPACK) ? (uint32_t)(dc).width     \\\n"
-           "                                 : (uint32_t)(dc).width * 8u)\n\n",
+           "#define JSTAGE %u\n#define JC %u\n\n",
            NL, NG, st.n_w64 > 0 ? st.n_w64 : 1, (unsigned)ph.n_aggs,
            st.hist_total > 0 ? st.hist_total : 1, (unsigned)st.stripes,
            (unsigned)st.stage_bytes, st.jcells);
   s += b;
-  s += "/* LDS-DMA stage of one block; the partial tail chunk is handled\n"
-       "   by the exec mask (the LDS destination must stay uniform +\n"
-       "   lane-linear for global_load_lds addressing) */\n"
-       "__device__ __forceinline__ void stage2(\n"
-       "    const uint8_t *__restrict__ buf, const dev_block &blk,\n"
-       "    uint8_t *dst) {\n"
-       "  const uint32_t n16 = (blk.block_len + 15) >> 4;\n"
-       "  const uint8_t *src = buf + blk.block_byte;\n"
-       "  for (uint32_t i = threadIdx.x; i < n16; i += WG) {\n"
-       "    __builtin_amdgcn_global_load_lds(\n"
-       "        (const __attribute__((address_space(1))) uint32_t\n"
-       "             *)(src + (size_t)i * 16),\n"
-       "        (__attribute__((address_space(3))) uint32_t\n"
-       "             *)(dst + (size_t)i * 16),\n"
-       "        16, 0, 0);\n"
-       "  }\n"
-       "}\n"
-       "/* 32-bit-offset packed read from an 8-B-aligned base */\n"
-       "__device__ __forceinline__ uint64_t jit_bread(\n"
-       "    const uint8_t *__restrict__ b, uint32_t bitpos, uint32_t k) {\n"
-       "  const uint64_t *w = (const uint64_t *)b;\n"
-       "  uint32_t widx = bitpos >> 6, sh = bitpos & 63;\n"
-       "  uint64_t v = w[widx] >> sh;\n"
-       "  if (sh + k > 64) v |= w[widx + 1] << (64 - sh);\n"
-       "  if (k < 64) v &= (((uint64_t)1 << k) - 1);\n"
-       "  return v;\n"
-       "}\n"
-       "/* the 32 bits at bitpos from a 4-B-aligned base (callers mask\n"
-       "   their fields out of it) */\n"
-       "__device__ __forceinline__ uint32_t jit_bread32(\n"
-       "    const uint8_t *__restrict__ b, uint32_t bitpos) {\n"
-       "  const uint32_t *w = (const uint32_t *)b;\n"
-       "  const uint32_t widx = bitpos >> 5;\n"
-       "  return __builtin_amdgcn_alignbit(w[widx + 1], w[widx], bitpos & "
-       "31);\n"
-       "}\n"
-      "__device__ __forceinline__ int jit_gslot(gslot *gt, uint64_t key) {\n"
-      "  uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - OBX_GTABLE_SHIFT)) &\n"
-      "                 (OBX_GTABLE_SLOTS - 1);\n"
-      "  for (int probe = 0; probe < OBX_GTABLE_SLOTS; probe++) {\n"
-      "    unsigned long long ck = atomicCAS(&gt[idx].key, OBX_KEY_EMPTY,\n"
-      "                                      (unsigned long long)key);\n"
-      "    if (ck == OBX_KEY_EMPTY || ck == key) return (int)idx;\n"
-      "    idx = (idx + 1) & (OBX_GTABLE_SLOTS - 1);\n"
-      "  }\n"
-      "  return -1;\n"
-      "}\n\n";
   snprintf(b, sizeof b,
            "/* Persistent-accumulator scan (the whole-kernel generalization\n"
            "   of the storage group-by pushdown, ObVectorStore::do_group_by):\n"
@@ -788,13 +717,8 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
            "    unsigned long long *__restrict__ counters) {\n",
            st.wpb);
   s += b;
-  const int sdb = st.sdb ? 1 : 0;
-  if (sdb)
-    s += "  __shared__ __attribute__((aligned(16))) uint8_t sega[JSTAGE],\n"
-         "      segb[JSTAGE];\n";
-  else
-    s += "  __shared__ __attribute__((aligned(16))) uint8_t "
-         "lds_blk[JSTAGE];\n";
+  s += "  __shared__ __attribute__((aligned(16))) uint8_t "
+       "lds_blk[JSTAGE];\n";
   s += ""
        "  __shared__ unsigned long long wacc64[NW64][JC][NSTRIPE];\n"
        "  __shared__ uint32_t hist[HTOT];\n";
@@ -971,23 +895,26 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   s += "  }\n"
        "  __syncthreads();\n"
        "\n";
-  if (st.skew) {
-    snprintf(b, sizeof b,
-             "  /* stagger co-resident WGs (~%u us apart) so their DMA\n"
-             "     and sweep phases interleave instead of convoying */\n"
-             "  for (uint32_t j2 = 0;\n"
-             "       j2 < ((blockIdx.x >> 8) & 7) * %uu; j2++)\n"
-             "    __builtin_amdgcn_s_sleep(15);\n",
-             (unsigned)st.skew, (unsigned)(st.skew * 3));
-    s += b;
-  }
-  /* ---- block loop ---- */
-  std::string body; /* per-block preamble + row sweep (emitted once for
-                       the single-buffer loop, twice for the overlapped
-                       2-phase loop) */
-  body += "    const uint64_t blk_bit = cur.block_byte * 8;\n"
+  /* ---- block loop: stage, per-block preamble, row sweep ---- */
+  s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
+       "gridDim.x) {\n"
+       "    const dev_block &cur = blocks[blk];\n"
+       "    const blk_leaf *bl = bleaves + (uint64_t)blk * (NL ? NL : "
+       "1);\n"
+       "    uint8_t blk_verdict = 1;\n"
+       "    for (uint32_t i = 0; i < NL; i++) {\n"
+       "      uint8_t c = leaf_class(cur, plan_leaves[i], bl[i]);\n"
+       "      if (c == 0) { blk_verdict = 0; break; }\n"
+       "      if (c == 2) blk_verdict = 2;\n"
+       "    }\n"
+       "    if (blk_verdict == 0) continue;\n"
+       "    __syncthreads(); /* drain previous block's LDS reads */\n"
+       "    stage2(buf, cur, lds_blk);\n"
+       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+       "    __syncthreads();\n";
+  s += "    const uint64_t blk_bit = cur.block_byte * 8;\n"
        "    blk_view bv;\n"
-       "    bv.base = stg;\n"
+       "    bv.base = lds_blk;\n"
        "    bv.bit_bias = blk_bit;\n"
        "    bv.rbase_bit = 0;\n"
        "    const uint32_t rows = cur.row_count;\n"
@@ -999,7 +926,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "    const uint32_t gW0 = PW(*gd0);\n"
              "    const uint32_t gn0 = gd0->count;\n",
              (unsigned)ph.need_cols[ph.group_idx[0]]);
-    body += b;
+    s += b;
   }
   if (NG > 1) {
     snprintf(b, sizeof b,
@@ -1009,7 +936,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "    const uint32_t gn1 = gd1->count;\n"
              "    const uint32_t dim0 = gn0 + 1;\n",
              (unsigned)ph.need_cols[ph.group_idx[1]]);
-    body += b;
+    s += b;
   }
   for (int j = 0; j < js.n_vc; j++) {
     if (st.vmode[j] == JV_REF) {
@@ -1020,20 +947,20 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                "    const uint32_t xn%d = cur.cols[%u].count;\n",
                j, (unsigned)js.vcol[j], j, (unsigned)js.vcol[j], j,
                (unsigned)js.vcol[j]);
-      body += b;
+      s += b;
     } else if (st.vraw8[j]) {
       snprintf(b, sizeof b,
                "    const uint32_t vb%d =\n"
                "        (uint32_t)((cur.cols[%u].data_bit >> 3) - "
                "cur.block_byte);\n",
                j, (unsigned)js.vcol[j]);
-      body += b;
+      s += b;
     } else {
       snprintf(b, sizeof b,
                "    const col_ctx c%d = make_col_ctx(cur.cols[%u], "
                "blk_bit);\n",
                j, (unsigned)js.vcol[j]);
-      body += b;
+      s += b;
     }
   }
   /* filter leaf preambles (always inline in v2) */
@@ -1045,12 +972,12 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
              i, i, i, (unsigned)st.leaf_cols[i], i,
              (unsigned)st.leaf_cols[i]);
-    body += b;
+    s += b;
     if (st.leaf_kind[i] == 1) {
       snprintf(b, sizeof b,
                "    const bool l%d_all = lb%d.mode == OBX_LEAF_ALL;\n", i,
                i);
-      body += b;
+      s += b;
     }
     if (st.r > 1 && st.leaf_multi[i]) {
       if (st.leaf_m32[i])
@@ -1059,15 +986,15 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
       else
         snprintf(b, sizeof b,
                  "    const uint64_t lm%d = (1ull << l%dW) - 1;\n", i, i);
-      body += b;
+      s += b;
     }
   }
   if (st.r > 1) {
     if (NG > 0 && st.g_multi[0])
-      body += st.g_m32[0] ? "    const uint32_t gm0 = (1u << gW0) - 1;\n"
+      s += st.g_m32[0] ? "    const uint32_t gm0 = (1u << gW0) - 1;\n"
                           : "    const uint64_t gm0 = (1ull << gW0) - 1;\n";
     if (NG > 1 && st.g_multi[1])
-      body += st.g_m32[1] ? "    const uint32_t gm1 = (1u << gW1) - 1;\n"
+      s += st.g_m32[1] ? "    const uint32_t gm1 = (1u << gW1) - 1;\n"
                           : "    const uint64_t gm1 = (1ull << gW1) - 1;\n";
     for (int j = 0; j < js.n_vc; j++)
       if (st.v_multi[j]) {
@@ -1077,7 +1004,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
         else
           snprintf(b, sizeof b,
                    "    const uint64_t xm%d = (1ull << xW%d) - 1;\n", j, j);
-        body += b;
+        s += b;
       }
   }
 
@@ -1246,15 +1173,13 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   acc += "        }\n";
 
   /* ---- row sweep (strip-mined; whole WG over the block) ---- */
-  std::string sweep2; /* emitted after the next block's DMA issue so the
-                         glds spans the whole row sweep */
   int R = st.r > 0 ? st.r : 1;
   snprintf(b, sizeof b,
            "    const uint32_t itersR = (rows + WG * %d - 1) / (WG * %d);\n"
            "    for (uint32_t it = 0; it < itersR; it++) {\n"
            "      const uint32_t rbase = (it * WG + tid) * %d;\n",
            R, R, R);
-  sweep2 += b;
+  s += b;
   for (int i = 0; i < NL; i++)
     if (st.leaf_multi[i]) {
       if (st.leaf_m32[i])
@@ -1267,7 +1192,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                  "      uint64_t wl%d = jit_bread(bv.base, l%do + rbase * "
                  "l%dW, %d * l%dW);\n",
                  i, i, i, R, i);
-      sweep2 += b;
+      s += b;
     }
   for (int g2 = 0; g2 < NG && g2 < 2; g2++) {
     if (!st.g_multi[g2]) continue;
@@ -1281,7 +1206,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                "      uint64_t wgr%d = jit_bread(bv.base, go%d + rbase * "
                "gW%d, %d * gW%d);\n",
                g2, g2, g2, R, g2);
-    sweep2 += b;
+    s += b;
   }
   for (int j = 0; j < js.n_vc; j++)
     if (st.v_multi[j]) {
@@ -1295,7 +1220,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                  "      uint64_t wx%d = jit_bread(bv.base, xo%d + rbase * "
                  "xW%d, %d * xW%d);\n",
                  j, j, j, R, j);
-      sweep2 += b;
+      s += b;
     }
   for (int j = 0; j < js.n_vc; j++)
     if (st.vmode[j] == JV_CTX && st.vraw8[j]) {
@@ -1303,7 +1228,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                "      const uint8_t *ep%d = bv.base + vb%d + (rbase << "
                "3);\n",
                j, j);
-      sweep2 += b;
+      s += b;
     }
   snprintf(b, sizeof b,
            "#pragma unroll\n"
@@ -1311,7 +1236,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
            "        const uint32_t r = rbase + k;\n"
            "        bool live = r < rows;\n",
            R);
-  sweep2 += b;
+  s += b;
   for (int i = 0; i < NL; i++) {
     if (st.leaf_kind[i] == 1) {
       if (st.leaf_multi[i])
@@ -1348,26 +1273,26 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                  "* l%dW, l%dW)) & 1;\n",
                  i, i, i, i);
     }
-    sweep2 += b;
+    s += b;
   }
   if (NG > 0) {
     if (st.r > 1 && st.g_multi[0])
-      sweep2 += "        uint32_t ref0 = (uint32_t)((wgr0 >> (k * gW0)) & "
+      s += "        uint32_t ref0 = (uint32_t)((wgr0 >> (k * gW0)) & "
            "gm0);\n";
     else
-      sweep2 += "        uint32_t ref0 = (uint32_t)jit_bread(bv.base, go0 + r * "
+      s += "        uint32_t ref0 = (uint32_t)jit_bread(bv.base, go0 + r * "
            "gW0, gW0);\n";
-    sweep2 += "        if (ref0 > gn0) ref0 = gn0;\n"
+    s += "        if (ref0 > gn0) ref0 = gn0;\n"
          "        uint32_t cell = ref0;\n";
   }
   if (NG > 1) {
     if (st.r > 1 && st.g_multi[1])
-      sweep2 += "        uint32_t ref1 = (uint32_t)((wgr1 >> (k * gW1)) & "
+      s += "        uint32_t ref1 = (uint32_t)((wgr1 >> (k * gW1)) & "
            "gm1);\n";
     else
-      sweep2 += "        uint32_t ref1 = (uint32_t)jit_bread(bv.base, go1 + r * "
+      s += "        uint32_t ref1 = (uint32_t)jit_bread(bv.base, go1 + r * "
            "gW1, gW1);\n";
-    sweep2 += "        if (ref1 > gn1) ref1 = gn1;\n"
+    s += "        if (ref1 > gn1) ref1 = gn1;\n"
          "        cell += ref1 * dim0;\n";
   }
   if (NG == 0) s += "        const uint32_t cell = 0;\n";
@@ -1385,7 +1310,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                  "+ r * xW%d, xW%d);\n"
                  "        if (x%d > xn%d) x%d = xn%d;\n",
                  j, j, j, j, j, j, j, j);
-      sweep2 += b;
+      s += b;
     } else if (st.vraw8[j]) {
       snprintf(b, sizeof b,
                "        int64_t v%d = *(const int64_t *)(ep%d + (k << "
@@ -1393,116 +1318,21 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                "        const bool nu%d = false;\n"
                "        (void)nu%d;\n",
                j, j, j, j);
-      sweep2 += b;
+      s += b;
     } else {
       snprintf(b, sizeof b,
                "        bool nu%d;\n"
                "        int64_t v%d = ctx_value(bv, c%d, r, nu%d);\n"
                "        (void)nu%d;\n",
                j, j, j, j, j);
-      sweep2 += b;
+      s += b;
     }
   }
-  sweep2 += acc;
-  sweep2 += "      }\n"
-       "    } /* row sweep */\n";
-  if (sdb) {
-    /* overlapped 2-phase loop: next block's LDS-DMA spans this block's
-       sweep (raw lgkm-only barriers; two distinct stage buffers --
-       hipcc drains glds to vmcnt(0) at __syncthreads and at aliased
-       LDS reads, see the filter JIT) */
-    s += "  uint32_t blkA = blockIdx.x;\n"
-         "  {\n"
-         "  uint8_t vA = 0;\n"
-         "  while (blkA < n_blocks) {\n"
-         "    const dev_block &nb = blocks[blkA];\n"
-         "    const blk_leaf *nbl = bleaves + (uint64_t)blkA * (NL ? NL : "
-         "1);\n"
-         "    vA = 1;\n"
-         "    for (uint32_t i = 0; i < NL; i++)\n"
-         "      if (leaf_class(nb, plan_leaves[i], nbl[i]) == 0) { vA = 0; "
-         "break; }\n"
-         "    if (vA) break;\n"
-         "    blkA += gridDim.x;\n"
-         "  }\n"
-         "  if (blkA < n_blocks) {\n"
-         "    stage2(buf, blocks[blkA], sega);\n"
-         "    for (;;) {\n";
-    const char *bufs2[2] = {"sega", "segb"};
-    for (int ph2 = 0; ph2 < 2; ph2++) {
-      snprintf(b, sizeof b,
-               "      {\n"
-               "      uint32_t blkN = blkA + gridDim.x;\n"
-               "      while (blkN < n_blocks) {\n"
-               "        const dev_block &nb = blocks[blkN];\n"
-               "        const blk_leaf *nbl = bleaves + (uint64_t)blkN * "
-               "(NL ? NL : 1);\n"
-               "        uint8_t v2 = 1;\n"
-               "        for (uint32_t i = 0; i < NL; i++)\n"
-               "          if (leaf_class(nb, plan_leaves[i], nbl[i]) == 0) "
-               "{ v2 = 0; break; }\n"
-               "        if (v2) break;\n"
-               "        blkN += gridDim.x;\n"
-               "      }\n"
-               "      asm volatile(\"s_waitcnt vmcnt(0)\" ::: "
-               "\"memory\");\n"
-               "      asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: "
-               "\"memory\");\n"
-               "      __builtin_amdgcn_s_barrier();\n"
-               "      const uint32_t blk = blkA;\n"
-               "      const dev_block &cur = blocks[blk];\n"
-               "      const blk_leaf *bl = bleaves + (uint64_t)blk * (NL ? "
-               "NL : 1);\n"
-               "      uint8_t blk_verdict = 1;\n"
-               "      for (uint32_t i = 0; i < NL; i++) {\n"
-               "        uint8_t c = leaf_class(cur, plan_leaves[i], "
-               "bl[i]);\n"
-               "        if (c == 2) { blk_verdict = 2; break; }\n"
-               "      }\n"
-               "      uint8_t *stg = %s;\n",
-               bufs2[ph2]);
-      s += b;
-      s += body; /* preamble: ordinary loads BEFORE the next issue */
-      snprintf(b, sizeof b,
-               "      if (blkN < n_blocks) stage2(buf, blocks[blkN], "
-               "%s);\n",
-               bufs2[ph2 ^ 1]);
-      s += b;
-      s += sweep2; /* ds-only row sweep: the glds spans it */
-      s += "      asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: "
-           "\"memory\");\n"
-           "      __builtin_amdgcn_s_barrier();\n"
-           "      if (blkN >= n_blocks) { blkA = n_blocks; break; }\n"
-           "      blkA = blkN;\n"
-           "      }\n";
-    }
-    s += "    }\n"
-         "  }\n"
-         "  }\n";
-  } else {
-  s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
-       "gridDim.x) {\n"
-       "    const dev_block &cur = blocks[blk];\n"
-       "    const blk_leaf *bl = bleaves + (uint64_t)blk * (NL ? NL : "
-       "1);\n"
-       "    uint8_t blk_verdict = 1;\n"
-       "    for (uint32_t i = 0; i < NL; i++) {\n"
-       "      uint8_t c = leaf_class(cur, plan_leaves[i], bl[i]);\n"
-       "      if (c == 0) { blk_verdict = 0; break; }\n"
-       "      if (c == 2) blk_verdict = 2;\n"
-       "    }\n"
-       "    if (blk_verdict == 0) continue;\n"
-       "    __syncthreads(); /* drain previous block's LDS reads */\n"
-       "    stage2(buf, cur, lds_blk);\n"
-       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-       "    __syncthreads();\n"
-       "    uint8_t *stg = lds_blk;\n";
-  s += body;
-  s += sweep2;
-  s += "  } /* blocks */\n";
-  }
+  s += acc;
+  s += "      }\n"
+       "    } /* row sweep */\n"
+       "  } /* blocks */\n";
   s += "\n"
-
        "\n"
        "  /* survivor count: wave-reduce, then stripe the global atomic\n"
        "     over 8 slots (same-address atomics serialize at L2) */\n"
@@ -1550,7 +1380,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "  /* workgroup partials [cell][agg]: {lo, hi} of an int128\n"
              "     sum, or {value, valid} of a min/max */\n"
              "  unsigned long long (*facc)[NAGGS][2] =\n"
-             "      (unsigned long long (*)[NAGGS][2])%s;\n"
+             "      (unsigned long long (*)[NAGGS][2])lds_blk;\n"
              "  for (uint32_t i = tid; i < JC * NAGGS; i += WG) {\n"
              "    const uint32_t a = i %% NAGGS;\n"
              "    facc[i / NAGGS][a][0] =\n"
@@ -1559,7 +1389,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "                             : 0ull;\n"
              "    facc[i / NAGGS][a][1] = 0;\n"
              "  }\n",
-             sdb ? "sega" : "lds_blk", f_min, f_max);
+             f_min, f_max);
     s += b;
   }
   s += "  /* flush pass 1: per-cell counts, keys -> global slots */\n"
@@ -1795,1091 +1625,4 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   }
   s += "}\n";
   return s;
-}
-
-/* ======================================================================
- * Filter-only JIT (obx_gpu_filter with want_row_ids == 0): wave-per-block
- * with NO LDS and NO barriers — each wave streams its block's FILTER
- * column bytes straight through L1/L2 (a filter touches only the leaf
- * streams, so staging whole blocks would read bytes nobody needs),
- * evaluates the inline leaf chain and writes the survivor bitmap with
- * two atomicOr per 64 rows. Eligibility: every leaf packed-range or
- * dict-mask (same classes as the scan kernel's inline filter).
- * ==================================================================== */
-
-static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
-                                const dev_leaf *pl, jit_strategy &st) {
-  const char *e = getenv("OBX_JIT_V2");
-  if (e && e[0] == '0') return false;
-  if (ph.n_leaves == 0 || ph.n_leaves > 4) return false;
-  /* AND/OR combine programs fold at CODEGEN: the postfix program is part
-     of the plan signature, so the kernel gets a single boolean
-     expression (the executor tree's shape, ob_pushdown_filter.cpp:1559,
-     evaluated branch-free per row) */
-  /* slice big blocks across waves so few-large-block sets still fill the
-     chip (16K wave slots at 8 WGs/CU) */
-  {
-    uint32_t want = 3u * 16384u;
-    uint32_t sl = h.n_blocks ? (want + h.n_blocks - 1) / h.n_blocks : 1;
-    const char *se = getenv("OBX_JIT_FSL");
-    if (se) sl = (uint32_t)atoi(se);
-    if (sl < 1) sl = 1;
-    if (sl > 16) sl = 16;
-    st.stripes = (uint8_t)sl; /* slice count for filter kernels */
-  }
-  uint32_t wmax = 0;
-  for (uint32_t i = 0; i < ph.n_leaves; i++) {
-    uint16_t col = pl[i].col;
-    bool mask_ok = pl[i].op != 10 || pl[i].n_bcols == 1;
-    if (h.col_dict_any[col] && mask_ok) st.leaf_kind[i] = 2;
-    else if (pl[i].op <= 6 && h.col_rangefam_every[col])
-      st.leaf_kind[i] = 1;
-    else return false;
-    st.leaf_cols[i] = col;
-    if (h.col_maxw[col] > wmax) wmax = h.col_maxw[col];
-  }
-  /* strip-mine R rows per lane: one packed read covers R fields when
-     R * max_width <= 64; narrow streams (dict refs, diff-coded dates)
-     would otherwise leave the kernel iteration-rate-bound */
-  {
-    const char *re = getenv("OBX_JIT_FR");
-    int r = re ? atoi(re) : (wmax && wmax * 4 <= 64 ? 4
-                             : wmax && wmax * 2 <= 64 ? 2 : 1);
-    if (r != 1 && r != 2 && r != 4) r = 1;
-    st.r = (uint8_t)r;
-    if (st.r > 1)
-      for (uint32_t i = 0; i < ph.n_leaves; i++)
-        st.leaf_multi[i] =
-            h.col_maxw[st.leaf_cols[i]] * st.r <= 64 ? 1 : 0;
-    /* software pipeline: hoist fu tiles' packed loads per superiteration
-       so each wave keeps several HBM fetches in flight (the PMC profile
-       shows the one-load-per-wave version is latency-bound at ~96% L2
-       miss with waves waiting ~41k cycles) */
-    const char *ue = getenv("OBX_JIT_FU");
-    int u = ue ? atoi(ue) : 4;
-    if (u < 1 || u > 8) u = 4;
-    st.fu = (uint8_t)u;
-    const char *pe = getenv("OBX_JIT_FPROBE");
-    st.fprobe = pe ? (uint8_t)atoi(pe) : 0;
-    const char *ske = getenv("OBX_JIT_SKEW");
-    st.skew = ske ? (uint8_t)atoi(ske) : 0;
-  }
-  /* staged mode: DMA each leaf's packed stream into LDS with
-     global_load_lds (the same engine the persistent scan kernel uses to
-     stream blocks at 3.4-4.5 TB/s) and evaluate from LDS -- plain
-     per-lane global loads of thin streams measured only 0.43-2.5 TB/s
-     (loads-only probe, profiles/r02) */
-  {
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < ph.n_leaves; i++) {
-      /* stream bytes + align-down slack(15) + jit_bread overread(8),
-         16-aligned */
-      uint64_t bits = (uint64_t)h.col_maxw[st.leaf_cols[i]] *
-                      (h.max_block_rows ? h.max_block_rows : 4096);
-      uint64_t seg = (((bits + 7) / 8) + 48) & ~15ull;
-      if (seg > 0xffffffffull) { total = 0xffffffffu; break; }
-      st.fseg[i] = (uint32_t)seg;
-      total += st.fseg[i];
-    }
-    const char *ge = getenv("OBX_JIT_FSTAGE");
-    bool want = !ge || ge[0] != '0';
-    if (want && total > 0 && total <= 18u * 1024u) st.fstage = 1;
-  }
-  /* combine programs are codegen-folded in the staged kernel only */
-  if (ph.n_prog && !st.fstage) return false;
-  st.leaf_inline = 1;
-  st.ok = true;
-  return true;
-}
-
-static std::string jit_fstrategy_sig(const dev_plan_hdr &ph,
-                                     const jit_strategy &st) {
-  char b[128];
-  std::string k = "F|";
-  const char *fnbe = getenv("OBX_JIT_FNB");
-  snprintf(b, sizeof b, "s%d|r%d|u%d|p%d|g%d:%u:%u:%u:%u|n%s|k%d|i%d|",
-           st.stripes, st.r, st.fu, st.fprobe, st.fstage, st.fseg[0],
-           st.fseg[1], st.fseg[2], st.fseg[3], fnbe ? fnbe : "-", st.skew,
-           st.frid);
-  k += b;
-  k += "P";
-  for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) {
-    snprintf(b, sizeof b, "%u.", ph.prog[p2]);
-    k += b;
-  }
-  k += "|";
-  b[0] = 0;
-  k += b;
-  for (uint32_t i = 0; i < ph.n_leaves; i++) {
-    snprintf(b, sizeof b, "L%d:%u:m%d|", st.leaf_kind[i], st.leaf_cols[i],
-             st.leaf_multi[i]);
-    k += b;
-  }
-  return k;
-}
-
-static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
-                                         const jit_strategy &st) {
-  const int NL = ph.n_leaves;
-  char b[1024];
-  std::string s;
-  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n\n";
-  snprintf(b, sizeof b,
-           "#define NL %d\n#define FSL %d\n#define FR %d\n"
-           "#define RID %d\n#define NCH %u\n"
-           "#define PW(dc)                                              \\\n"
-           "  (((dc).flags & OBX_DF_BITPACK) ? (uint32_t)(dc).width     \\\n"
-           "                                 : (uint32_t)(dc).width * 8u)\n",
-           NL, st.stripes > 0 ? st.stripes : 1, st.r > 0 ? st.r : 1,
-           st.frid ? 1 : 0, (unsigned)(st.fnch ? st.fnch : 1));
-  s += b;
-  s += "__device__ __forceinline__ uint64_t jit_bread(\n"
-       "    const uint8_t *__restrict__ b, uint32_t bitpos, uint32_t k) {\n"
-       "  const uint64_t *w = (const uint64_t *)b;\n"
-       "  uint32_t widx = bitpos >> 6, sh = bitpos & 63;\n"
-       "  uint64_t v = w[widx] >> sh;\n"
-       "  if (sh + k > 64) v |= w[widx + 1] << (64 - sh);\n"
-       "  if (k < 64) v &= (((uint64_t)1 << k) - 1);\n"
-       "  return v;\n"
-       "}\n"
-       "__device__ __forceinline__ uint8_t f3and(uint8_t a, uint8_t b) {\n"
-       "  return (a == 0 || b == 0) ? 0 : ((a == 1 && b == 1) ? 1 : 2);\n"
-       "}\n"
-       "__device__ __forceinline__ uint8_t f3or(uint8_t a, uint8_t b) {\n"
-       "  return (a == 1 || b == 1) ? 1 : ((a == 0 && b == 0) ? 0 : 2);\n"
-       "}\n";
-  /* codegen folds of the postfix combine program (plan data, so the
-     kernel gets one closed-form expression) */
-  auto fold_prog = [&](const char *item_fmt, bool boolean) {
-    char t[96];
-    if (ph.n_prog == 0) {
-      std::string e = boolean ? "(" : "";
-      for (int i2 = 0; i2 < NL; i2++) {
-        snprintf(t, sizeof t, item_fmt, i2);
-        if (boolean) {
-          if (i2) e += " && ";
-          e += t;
-        } else {
-          e = i2 == 0 ? t : ("f3and(" + e + ", " + t + ")");
-        }
-      }
-      if (boolean) e += ")";
-      return e;
-    }
-    std::string stk[16];
-    int sp = 0;
-    for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) {
-      uint8_t tok = ph.prog[p2];
-      if (tok < ph.n_leaves) {
-        snprintf(t, sizeof t, item_fmt, (int)tok);
-        stk[sp++] = t;
-      } else {
-        std::string b2 = stk[--sp], a2 = stk[sp - 1];
-        if (boolean)
-          stk[sp - 1] =
-              "(" + a2 + (tok == 128 ? " && " : " || ") + b2 + ")";
-        else
-          stk[sp - 1] = (tok == 128 ? "f3and(" : "f3or(") + a2 + ", " +
-                        b2 + ")";
-      }
-    }
-    return stk[0];
-  };
-  if (st.fstage) {
-    /* ---- staged mode: WG per block, leaf streams DMA'd to LDS; when
-       two buffers fit the LDS budget the next block's DMA overlaps the
-       current block's sweep (uniform buffer parity: the LDS-DMA
-       destination stays uniform + lane-linear) ---- */
-    uint32_t off[4] = {}, total = 0;
-    for (int i = 0; i < NL; i++) { off[i] = total; total += st.fseg[i]; }
-    /* batch NB blocks per stage round: amortizes the per-block
-       vmcnt(0) drain + barriers that serialize WGs into convoys (the
-       per-block wall time measured constant ~7.5us regardless of block
-       bytes) */
-    int NB = 1; /* batching A/B'd worse: LDS growth costs occupancy */
-    if (const char *ne = getenv("OBX_JIT_FNB")) {
-      int v = atoi(ne);
-      if (v >= 1 && v <= 8 && (uint32_t)v * total <= 64u * 1024u) NB = v;
-    }
-    /* double-buffer with RAW s_barrier: hipcc drains every in-flight
-       global_load_lds to vmcnt(0) before a __syncthreads(), so the naive
-       double-buffer overlapped nothing (measured identical); with
-       lgkmcnt-only barriers the next block's DMA spans the sweep */
-    /* measured: even with the glds span achieved in ISA, overlap buys
-       nothing here — the strided stage pattern caps at ~2.4 TB/s with
-       or without it (profiles/r02) — so default off */
-    int DB2 = 0;
-    if (const char *de2 = getenv("OBX_JIT_FDB2")) DB2 = atoi(de2) ? 1 : 0;
-    if (DB2 && (NB > 1 || 2u * total > 64u * 1024u)) DB2 = 0;
-    if (DB2 && 2u * total > 64u * 1024u) DB2 = 0;
-    snprintf(b, sizeof b,
-             "#define SEGSZ %uu\n#define FNB %d\n#define FDB2 %d\n",
-             total, DB2 ? 1 : NB, DB2);
-    s += b;
-    s += "struct blkp {\n"
-         "  const uint8_t *bp;\n"
-         "  uint64_t row0;\n"
-         "  uint32_t blk, rows;\n";
-    snprintf(b, sizeof b,
-             "  uint32_t W[%d], bit[%d], lo[%d], len[%d];\n"
-             "  /* leaf payload in registers: the sweep must issue no\n"
-             "     ordinary global load while the next block'\''s LDS-DMA\n"
-             "     is in flight (its first use would drain vmcnt to 0) */\n"
-             "  unsigned long long lmask[%d];\n"
-             "  long long llo[%d], lhi[%d];\n"
-             "  uint8_t linv[%d], lall[%d], lnone[%d];\n"
-             "};\n",
-             NL, NL, NL, NL, NL, NL, NL, NL, NL, NL);
-    s += b;
-    s += "__device__ __forceinline__ bool load_params(\n"
-         "    const uint8_t *__restrict__ buf,\n"
-         "    const dev_block *__restrict__ blocks,\n"
-         "    const dev_leaf *__restrict__ plan_leaves,\n"
-         "    const blk_leaf *__restrict__ bleaves, uint32_t blk,\n"
-         "    blkp &p) {\n"
-         "  const dev_block &cur = blocks[blk];\n"
-         "  const blk_leaf *bl = bleaves + (size_t)blk * NL;\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  const uint8_t c%d = leaf_class(cur, plan_leaves[%d], "
-               "bl[%d]);\n",
-               i, i, i);
-      s += b;
-    }
-    s += "  if ((" + fold_prog("c%d", false) + ") == 0) return false;\n";
-    s += ""
-         "  p.blk = blk;\n"
-         "  p.rows = cur.row_count;\n"
-         "  p.row0 = dev_block_row_start(&cur);\n"
-         "  p.bp = buf + cur.block_byte;\n"
-         "  const uint64_t blk_bit = cur.block_byte * 8;\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  {\n"
-               "    const uint32_t o = (uint32_t)(cur.cols[%u].data_bit - "
-               "blk_bit);\n"
-               "    const uint32_t W = PW(cur.cols[%u]);\n"
-               "    const uint32_t lo = (o >> 3) & ~15u;\n"
-               "    p.W[%d] = W;\n"
-               "    p.lo[%d] = lo;\n"
-               "    p.bit[%d] = o - lo * 8;\n"
-               "    p.len[%d] = ((((o + p.rows * W + 7) >> 3) - lo) + 15) & "
-               "~15u;\n"
-               "  }\n",
-               (unsigned)st.leaf_cols[i], (unsigned)st.leaf_cols[i], i, i,
-               i, i);
-      s += b;
-    }
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  p.lmask[%d] = bl[%d].mask;\n"
-               "  p.llo[%d] = bl[%d].lo;\n"
-               "  p.lhi[%d] = bl[%d].hi;\n"
-               "  p.linv[%d] = bl[%d].invert;\n"
-               "  p.lall[%d] = bl[%d].mode == OBX_LEAF_ALL ? 1 : 0;\n"
-               "  p.lnone[%d] = bl[%d].mode == OBX_LEAF_NONE ? 1 : 0;\n",
-               i, i, i, i, i, i, i, i, i, i, i, i);
-      s += b;
-    }
-    s += "  return true;\n"
-         "}\n"
-         "__device__ __forceinline__ void issue_stage(\n"
-         "    const blkp &p, uint8_t *dst, uint32_t tid) {\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  for (uint32_t i2 = tid; i2 * 16 < p.len[%d]; i2 += WG)\n"
-               "    __builtin_amdgcn_global_load_lds(\n"
-               "        (const __attribute__((address_space(1))) uint32_t\n"
-               "             *)(p.bp + p.lo[%d] + (size_t)i2 * 16),\n"
-               "        (__attribute__((address_space(3))) uint32_t\n"
-               "             *)(dst + %uu + (size_t)i2 * 16),\n"
-               "        16, 0, 0);\n",
-               i, i, off[i]);
-      s += b;
-    }
-    s += "}\n";
-    /* sweep of one staged block, as a string emitted twice (db/sb) */
-    std::string sweep;
-    if (st.fprobe == 2) {
-      /* stage-only probe: consume one staged byte so DMA isn't dead */
-      sweep = "      lane_cnt += SGB[lane] & 1;\n";
-    } else {
-    sweep += "      {\n";
-    for (int i = 0; i < NL; i++) {
-      if (st.leaf_kind[i] == 1) {
-        snprintf(b, sizeof b,
-                 "      const bool l%d_all = cur.lall[%d] != 0;\n", i, i);
-        sweep += b;
-      }
-    }
-    const int SR = st.r > 1 ? st.r : 1;
-    if (SR > 1) {
-      /* strip-mined LDS sweep: one packed ds_read covers SR fields,
-         mask assembled via wave-synchronous LDS ORs (as direct mode) */
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(b, sizeof b,
-                   "      const uint64_t lmk%d =\n"
-                   "          ((uint64_t)1 << cur.W[%d]) - 1;\n",
-                   i, i);
-          sweep += b;
-        }
-      sweep +=
-          "      const uint32_t rows = cur.rows;\n"
-          "      const uint64_t row0 = cur.row0;\n"
-          "      const uint32_t tiles = (rows + 64 * FR - 1) / (64 * "
-          "FR);\n"
-          "      for (uint32_t t = wv; t < tiles; t += WAVES) {\n"
-          "        const uint32_t rt = t * 64 * FR + lane * FR;\n"
-          "        if (lane < FR) fm[wv][lane] = 0;\n";
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(b, sizeof b,
-                   "        uint64_t wl%d = (rt < rows)\n"
-                   "            ? jit_bread(SGB + %uu, cur.bit[%d] + rt * "
-                   "cur.W[%d], FR * cur.W[%d])\n"
-                   "            : 0;\n",
-                   i, off[i], i, i, i);
-          sweep += b;
-        }
-      sweep += "        uint32_t pm = 0;\n"
-               "#pragma unroll\n"
-               "        for (uint32_t k = 0; k < FR; k++) {\n"
-               "          const uint32_t r = rt + k;\n"
-               "          bool live = r < rows;\n";
-      if (ph.n_prog) {
-        sweep += "          if (live) {\n";
-        for (int i = 0; i < NL; i++) {
-          if (st.leaf_kind[i] == 1) {
-            if (st.leaf_multi[i])
-              snprintf(b, sizeof b,
-                       "          uint64_t v%d = ((wl%d >> (k * cur.W[%d]))"
-                       " & lmk%d) ^ cur.lmask[%d];\n"
-                       "          const bool lf%d = !cur.lnone[%d] &&\n"
-                       "              (l%d_all || (((v%d - cur.llo[%d]) <= "
-                       "(cur.lhi[%d] - cur.llo[%d])) != "
-                       "(bool)cur.linv[%d]));\n",
-                       i, i, i, i, i, i, i, i, i, i, i, i, i);
-            else
-              snprintf(b, sizeof b,
-                       "          uint64_t v%d = jit_bread(SGB + %uu, "
-                       "cur.bit[%d] + r * cur.W[%d], cur.W[%d]) ^ "
-                       "cur.lmask[%d];\n"
-                       "          const bool lf%d = !cur.lnone[%d] &&\n"
-                       "              (l%d_all || (((v%d - cur.llo[%d]) <= "
-                       "(cur.lhi[%d] - cur.llo[%d])) != "
-                       "(bool)cur.linv[%d]));\n",
-                       i, off[i], i, i, i, i, i, i, i, i, i, i, i, i);
-          } else {
-            if (st.leaf_multi[i])
-              snprintf(b, sizeof b,
-                       "          const bool lf%d = (cur.lmask[%d] >>\n"
-                       "              (uint32_t)((wl%d >> (k * cur.W[%d])) "
-                       "& lmk%d)) & 1;\n",
-                       i, i, i, i, i);
-            else
-              snprintf(b, sizeof b,
-                       "          const bool lf%d = (cur.lmask[%d] >>\n"
-                       "              (uint32_t)jit_bread(SGB + %uu, "
-                       "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                       i, i, off[i], i, i, i);
-          }
-          sweep += b;
-        }
-        sweep += "          live = " + fold_prog("lf%d", true) + ";\n"
-                 "          }\n";
-      } else {
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 1) {
-          if (st.leaf_multi[i])
-            snprintf(b, sizeof b,
-                     "          if (live && !l%d_all) {\n"
-                     "            uint64_t v = ((wl%d >> (k * cur.W[%d])) "
-                     "& lmk%d) ^ cur.lmask[%d];\n"
-                     "            live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                     "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                     "          }\n",
-                     i, i, i, i, i, i, i, i, i);
-          else
-            snprintf(b, sizeof b,
-                     "          if (live && !l%d_all) {\n"
-                     "            uint64_t v = jit_bread(SGB + %uu, "
-                     "cur.bit[%d] + r * cur.W[%d], cur.W[%d]) ^ "
-                     "cur.lmask[%d];\n"
-                     "            live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                     "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                     "          }\n",
-                     i, off[i], i, i, i, i, i, i, i, i);
-        } else {
-          if (st.leaf_multi[i])
-            snprintf(b, sizeof b,
-                     "          if (live)\n"
-                     "            live = (cur.lmask[%d] >>\n"
-                     "                    (uint32_t)((wl%d >> (k * "
-                     "cur.W[%d])) & lmk%d)) & 1;\n",
-                     i, i, i, i);
-          else
-            snprintf(b, sizeof b,
-                     "          if (live)\n"
-                     "            live = (cur.lmask[%d] >>\n"
-                     "                    (uint32_t)jit_bread(SGB + %uu, "
-                     "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                     i, off[i], i, i, i);
-        }
-        sweep += b;
-      }
-      }
-      snprintf(b, sizeof b,
-               "          pm |= live ? (1u << k) : 0u;\n"
-               "        }\n"
-               "        lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
-               "        if (pm)\n"
-               "          atomicOr(&fm[wv][lane >> %d],\n"
-               "                   (unsigned long long)pm << ((lane & %uu) "
-               "* FR));\n"
-               "#if RID\n"
-               "        if (lane < FR && t * FR + lane < NCH)\n"
-               "          cmask[t * FR + lane] = fm[wv][lane];\n"
-               "#endif\n"
-               "        if (lane < FR) {\n"
-               "          unsigned long long m = fm[wv][lane];\n"
-               "          if (m) {\n"
-               "            const uint64_t pos =\n"
-               "                row0 + (uint64_t)t * (64 * FR) + lane * "
-               "64;\n"
-               "            const uint64_t w0 = pos >> 6;\n"
-               "            const uint32_t sh = (uint32_t)(pos & 63);\n"
-               "            atomicOr(&bitmap[w0], m << sh);\n"
-               "            if (sh && (m >> (64 - sh)))\n"
-               "              atomicOr(&bitmap[w0 + 1], m >> (64 - "
-               "sh));\n"
-               "          }\n"
-               "        }\n"
-               "      }\n"
-               "      }\n",
-               SR == 4 ? 4 : 5, SR == 4 ? 15u : 31u);
-      sweep += b;
-    } else {
-    sweep += "      const uint32_t rows = cur.rows;\n"
-             "      const uint64_t row0 = cur.row0;\n"
-             "      const uint32_t n64 = (rows + 63) >> 6;\n"
-             "      for (uint32_t it = wv; it < n64; it += WAVES) {\n"
-             "        const uint32_t r = it * 64 + lane;\n"
-             "        bool live = r < rows;\n";
-    if (ph.n_prog) {
-      sweep += "        if (live) {\n";
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 1)
-          snprintf(b, sizeof b,
-                   "        uint64_t v%d = jit_bread(SGB + %uu, cur.bit[%d]"
-                   " + r * cur.W[%d], cur.W[%d]) ^ cur.lmask[%d];\n"
-                   "        const bool lf%d = !cur.lnone[%d] &&\n"
-                   "            (l%d_all || (((v%d - cur.llo[%d]) <= "
-                   "(cur.lhi[%d] - cur.llo[%d])) != "
-                   "(bool)cur.linv[%d]));\n",
-                   i, off[i], i, i, i, i, i, i, i, i, i, i, i, i);
-        else
-          snprintf(b, sizeof b,
-                   "        const bool lf%d = (cur.lmask[%d] >>\n"
-                   "            (uint32_t)jit_bread(SGB + %uu, cur.bit[%d] "
-                   "+ r * cur.W[%d], cur.W[%d])) & 1;\n",
-                   i, i, off[i], i, i, i);
-        sweep += b;
-      }
-      sweep += "        live = " + fold_prog("lf%d", true) + ";\n"
-               "        }\n";
-    } else {
-    for (int i = 0; i < NL; i++) {
-      if (st.leaf_kind[i] == 1)
-        snprintf(b, sizeof b,
-                 "        if (live && !l%d_all) {\n"
-                 "          uint64_t v = jit_bread(SGB + %uu, cur.bit[%d] + "
-                 "r * cur.W[%d], cur.W[%d]) ^ cur.lmask[%d];\n"
-                 "          live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                 "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                 "        }\n",
-                 i, off[i], i, i, i, i, i, i, i, i);
-      else
-        snprintf(b, sizeof b,
-                 "        if (live)\n"
-                 "          live = (cur.lmask[%d] >>\n"
-                 "                  (uint32_t)jit_bread(SGB + %uu, "
-                 "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                 i, off[i], i, i, i);
-      sweep += b;
-    }
-    }
-    sweep += "        uint64_t m = __ballot(live);\n"
-             "#if RID\n"
-             "        if (lane == 0 && it < NCH) cmask[it] = m;\n"
-             "#endif\n"
-             "        lane_cnt += live ? 1u : 0u;\n"
-             "        if (lane == 0 && m) {\n"
-             "          const uint64_t pos = row0 + (uint64_t)it * 64;\n"
-             "          const uint64_t w0 = pos >> 6;\n"
-             "          const uint32_t sh = (uint32_t)(pos & 63);\n"
-             "          atomicOr(&bitmap[w0], m << sh);\n"
-             "          if (sh && (m >> (64 - sh)))\n"
-             "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
-             "        }\n"
-             "      }\n"
-             "      }\n";
-    }
-    }
-    auto stage_with = [&](const char *pv, const char *bufname) {
-      std::string o;
-      char bb[512];
-      for (int i = 0; i < NL; i++) {
-        snprintf(bb, sizeof bb,
-                 "      for (uint32_t i2 = tid; i2 * 16 < %s.len[%d]; i2 "
-                 "+= WG)\n"
-                 "        __builtin_amdgcn_global_load_lds(\n"
-                 "            (const __attribute__((address_space(1))) "
-                 "uint32_t\n"
-                 "                 *)(%s.bp + %s.lo[%d] + (size_t)i2 * "
-                 "16),\n"
-                 "            (__attribute__((address_space(3))) "
-                 "uint32_t\n"
-                 "                 *)(%s + %uu + (size_t)i2 * 16),\n"
-                 "            16, 0, 0);\n",
-                 pv, i, pv, pv, i, bufname, off[i]);
-        o += bb;
-      }
-      return o;
-    };
-    if (st.frid) {
-      sweep +=
-          "#if RID\n"
-          "      /* ordered selection vectors from the captured chunk\n"
-          "         masks (get_row_ids shape: block-local int32 row ids\n"
-          "         at the block's absolute row offset) */\n"
-          "      __syncthreads();\n"
-          "      if (tid == 0) {\n"
-          "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
-          "        uint32_t acc = 0;\n"
-          "        for (uint32_t c2 = 0; c2 < n64r; c2++) {\n"
-          "          cpre[c2] = acc;\n"
-          "          acc += (uint32_t)__popcll(cmask[c2]);\n"
-          "        }\n"
-          "        blk_counts[cur.blk] = acc;\n"
-          "      }\n"
-          "      __syncthreads();\n"
-          "      {\n"
-          "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
-          "        for (uint32_t c2 = wv; c2 < n64r; c2 += WAVES) {\n"
-          "          const unsigned long long m2 = cmask[c2];\n"
-          "          if ((m2 >> lane) & 1) {\n"
-          "            const uint32_t pos = cpre[c2] +\n"
-          "                (uint32_t)__popcll(m2 &\n"
-          "                    (((unsigned long long)1 << lane) - 1));\n"
-          "            row_ids[cur.row0 + pos] = (int32_t)(c2 * 64 + "
-          "lane);\n"
-          "          }\n"
-          "        }\n"
-          "      }\n"
-          "#endif\n";
-    }
-    auto sweep_with = [&](const char *bufname) {
-      std::string t = sweep;
-      size_t p2 = 0;
-      while ((p2 = t.find("SGB", p2)) != std::string::npos) {
-        t.replace(p2, 3, bufname);
-        p2 += strlen(bufname);
-      }
-      return t;
-    };
-    if (st.fprobe == 1) {
-      /* no-flush probe: strip the global bitmap atomics */
-      std::string t; size_t p0 = 0;
-      while (p0 < sweep.size()) {
-        size_t p1 = sweep.find("atomicOr(&bitmap", p0);
-        if (p1 == std::string::npos) { t += sweep.substr(p0); break; }
-        size_t p2 = sweep.find(";\n", p1);
-        t += sweep.substr(p0, p1 - p0);
-        t += "(void)0;\n";
-        p0 = p2 + 2;
-      }
-      sweep = t;
-    }
-    s += "extern \"C\" __global__ __launch_bounds__(256, 8) void "
-         "k_jit_filter(\n"
-         "    const uint8_t *__restrict__ buf, const dev_block "
-         "*__restrict__ blocks,\n"
-         "    uint32_t n_blocks, const dev_leaf *__restrict__ "
-         "plan_leaves,\n"
-         "    const blk_leaf *__restrict__ bleaves,\n"
-         "    unsigned long long *__restrict__ bitmap,\n"
-         "    int32_t *__restrict__ row_ids,\n"
-         "    uint32_t *__restrict__ blk_counts,\n"
-         "    unsigned long long *__restrict__ counters) {\n"
-         "  const uint32_t tid = threadIdx.x;\n"
-         "  const uint32_t lane = tid & 63, wv = tid >> 6;\n"
-         "  uint32_t lane_cnt = 0;\n"
-         "#if FDB2\n"
-         "  __shared__ uint8_t segA[SEGSZ], segB[SEGSZ];\n"
-         "#else\n"
-         "  __shared__ uint8_t seg[SEGSZ * FNB];\n"
-         "#endif\n"
-         "#if FR > 1\n"
-         "  __shared__ unsigned long long fm[WAVES][FR];\n"
-         "#endif\n"
-         "#if RID\n"
-         "  __shared__ unsigned long long cmask[NCH];\n"
-         "  __shared__ uint32_t cpre[NCH];\n"
-         "#endif\n"
-         "  __shared__ unsigned long long wsum;\n"
-         "  if (tid == 0) wsum = 0;\n";
-  if (st.skew) {
-    snprintf(b, sizeof b,
-             "  for (uint32_t j2 = 0;\n"
-             "       j2 < ((blockIdx.x >> 8) & 7) * %uu; j2++)\n"
-             "    __builtin_amdgcn_s_sleep(15);\n",
-             (unsigned)(st.skew * 3));
-    s += b;
-  }
-  s += "  uint32_t bi = blockIdx.x;\n"
-         "  const uint32_t gstep = gridDim.x;\n";
-    if (DB2) {
-      /* two distinct LDS arrays + a 2-phase unrolled loop: a runtime
-         buffer-parity pointer defeats alias analysis, and hipcc then
-         orders the sweep's ds_reads after the in-flight glds with a
-         vmcnt(0) (seen in ISA) — static array references let the DMA
-         truly span the sweep */
-      s += "  blkp cur;\n"
-           "  while (bi < n_blocks &&\n"
-           "         !load_params(buf, blocks, plan_leaves, bleaves, bi, "
-           "cur))\n"
-           "    bi += gstep;\n"
-           "  if (bi < n_blocks) {\n";
-    {
-      std::string t = stage_with("cur", "segA");
-      /* top-level indentation: staged pre-loop */
-      s += t;
-    }
-    s += "    for (;;) {\n";
-      const char *bufs[2] = {"segA", "segB"};
-      for (int ph2 = 0; ph2 < 2; ph2++) {
-        snprintf(b, sizeof b,
-                 "      {\n"
-                 "      uint32_t bj = bi + gstep;\n"
-                 "      blkp nxt;\n"
-                 "      while (bj < n_blocks &&\n"
-                 "             !load_params(buf, blocks, plan_leaves, "
-                 "bleaves, bj, nxt))\n"
-                 "        bj += gstep;\n"
-                 "      asm volatile(\"s_waitcnt vmcnt(0)\" ::: "
-                 "\"memory\");\n"
-                 "      asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: "
-                 "\"memory\");\n"
-                 "      __builtin_amdgcn_s_barrier();\n"
-                 "      if (bj < n_blocks) {\n");
-        s += b;
-        s += stage_with("nxt", bufs[ph2 ^ 1]);
-        s += "      }\n";
-        s += sweep_with(bufs[ph2]);
-        s += "      asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: "
-             "\"memory\");\n"
-             "      __builtin_amdgcn_s_barrier();\n"
-             "      if (bj >= n_blocks) break;\n"
-             "      cur = nxt;\n"
-             "      bi = bj;\n"
-             "      }\n";
-      }
-      s += "    }\n"
-           "  }\n";
-    } else {
-    s += "  for (;;) {\n";
-    for (int j = 0; j < NB; j++) {
-      snprintf(b, sizeof b,
-               "    bool v%d = false;\n"
-               "    blkp pb%d;\n"
-               "    while (bi < n_blocks) {\n"
-               "      bool ok = load_params(buf, blocks, plan_leaves, "
-               "bleaves, bi, pb%d);\n"
-               "      bi += gstep;\n"
-               "      if (ok) { v%d = true; break; }\n"
-               "    }\n",
-               j, j, j, j);
-      s += b;
-    }
-    s += "    if (!v0) break;\n"
-         "    __syncthreads(); /* drain previous sweep's LDS reads */\n";
-    for (int j = 0; j < NB; j++) {
-      snprintf(b, sizeof b,
-               "    if (v%d) issue_stage(pb%d, seg + %d * SEGSZ, tid);\n",
-               j, j, j);
-      s += b;
-    }
-    s += "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-         "    __syncthreads();\n";
-    for (int j = 0; j < NB; j++) {
-      snprintf(b, sizeof b,
-               "    if (v%d) {\n"
-               "      const blkp &cur = pb%d;\n"
-               "      uint8_t *sg = seg + %d * SEGSZ;\n",
-               j, j, j);
-      s += b;
-      s += sweep_with("sg");
-      s += "    }\n";
-    }
-    snprintf(b, sizeof b, "    if (!v%d) break;\n", NB - 1);
-    s += b;
-    s += "  }\n";
-    }
-    s += ""
-         "  /* one global atomic per WG into a slot striped by blockIdx:\n"
-         "     16k same-address atomics serialized ~0.2 ms at L2 */\n"
-         "  for (int off2 = 32; off2 > 0; off2 >>= 1)\n"
-         "    lane_cnt += (uint32_t)__shfl_xor((int)lane_cnt, off2, 64);\n"
-         "  __syncthreads();\n"
-         "  if (lane == 0 && lane_cnt)\n"
-         "    atomicAdd(&wsum, (unsigned long long)lane_cnt);\n"
-         "  __syncthreads();\n"
-         "  if (tid == 0 && wsum)\n"
-         "    atomicAdd(&counters[8 + (blockIdx.x & 7)], wsum);\n"
-         "}\n";
-    return s;
-  }
-  s += "extern \"C\" __global__ __launch_bounds__(256, 8) void "
-       "k_jit_filter(\n"
-       "    const uint8_t *__restrict__ buf, const dev_block *__restrict__ "
-       "blocks,\n"
-       "    uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,\n"
-       "    const blk_leaf *__restrict__ bleaves,\n"
-       "    unsigned long long *__restrict__ bitmap,\n"
-       "    int32_t *__restrict__ row_ids,\n"
-       "    uint32_t *__restrict__ blk_counts,\n"
-       "    unsigned long long *__restrict__ counters) {\n"
-       "  const uint32_t tid = threadIdx.x;\n"
-       "  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;\n"
-       "  uint32_t lane_cnt = 0;\n"
-       "  __shared__ unsigned long long wsum;\n"
-       "  if (tid == 0) wsum = 0;\n"
-       "#if FR > 1\n"
-       "  __shared__ unsigned long long fm[WAVES][FR];\n"
-       "#endif\n"
-       "  const uint64_t n_work = (uint64_t)n_blocks * FSL;\n"
-       "  for (uint64_t w = (uint64_t)blockIdx.x * WAVES + wv;\n"
-       "       w < n_work; w += (uint64_t)gridDim.x * WAVES) {\n"
-       "    const uint64_t blk = w / FSL;\n"
-       "    const uint32_t sl = (uint32_t)(w % FSL);\n"
-       "    const dev_block &cur = blocks[blk];\n"
-       "    const blk_leaf *bl = bleaves + blk * NL;\n"
-       "    uint8_t blk_verdict = 1;\n"
-       "    for (uint32_t i = 0; i < NL; i++) {\n"
-       "      uint8_t c = leaf_class(cur, plan_leaves[i], bl[i]);\n"
-       "      if (c == 0) { blk_verdict = 0; break; }\n"
-       "      if (c == 2) blk_verdict = 2;\n"
-       "    }\n"
-       "    if (blk_verdict == 0) continue;\n"
-       "    const uint8_t *bp = buf + cur.block_byte;\n"
-       "    const uint64_t blk_bit = cur.block_byte * 8;\n"
-       "    const uint32_t all_rows = cur.row_count;\n"
-       "    /* 64-aligned row slice of this block */\n"
-       "    const uint32_t chunk =\n"
-       "        ((all_rows + FSL * 64 - 1) / (FSL * 64)) * 64;\n"
-       "    const uint32_t rbeg = sl * chunk;\n"
-       "    if (rbeg >= all_rows) continue;\n"
-       "    const uint32_t rend =\n"
-       "        (rbeg + chunk < all_rows) ? rbeg + chunk : all_rows;\n"
-       "    const uint64_t row0 = dev_block_row_start(&cur) + rbeg;\n";
-  for (int i = 0; i < NL; i++) {
-    snprintf(b, sizeof b,
-             "    const blk_leaf lb%d = bl[%d];\n"
-             "    const uint32_t l%do =\n"
-             "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
-             "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
-             i, i, i, (unsigned)st.leaf_cols[i], i,
-             (unsigned)st.leaf_cols[i]);
-    s += b;
-    if (st.leaf_kind[i] == 1) {
-      snprintf(b, sizeof b,
-               "    const bool l%d_all = lb%d.mode == OBX_LEAF_ALL;\n", i, i);
-      s += b;
-    }
-  }
-  const int R = st.r > 1 ? st.r : 1;
-  if (R > 1) {
-    for (int i = 0; i < NL; i++)
-      if (st.leaf_multi[i]) {
-        snprintf(b, sizeof b,
-                 "    const uint64_t lmk%d = ((uint64_t)1 << l%dW) - 1;\n",
-                 i, i);
-        s += b;
-      }
-    const int FU = st.fu > 0 ? st.fu : 1;
-    /* tile = 64*FR rows per wave; `emit_pre` issues the tile's packed
-       loads, `emit_tile` consumes them — the superiteration emits FU
-       pre-blocks before any tile body so each wave keeps FU independent
-       HBM fetches in flight (in-order vmcnt retirement pipelines them) */
-    auto emit_pre = [&](const std::string &sfx, const std::string &itx) {
-      std::string o;
-      char bb[512];
-      snprintf(bb, sizeof bb,
-               "      const uint32_t rt%s = rbeg + (%s) * 64 * FR + lane * "
-               "FR;\n",
-               sfx.c_str(), itx.c_str());
-      o += bb;
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(bb, sizeof bb,
-                   "      uint64_t wl%d%s = (rt%s < rend)\n"
-                   "          ? jit_bread(bp, l%do + rt%s * l%dW, FR * "
-                   "l%dW)\n"
-                   "          : 0;\n",
-                   i, sfx.c_str(), sfx.c_str(), i, sfx.c_str(), i, i);
-          o += bb;
-        }
-      return o;
-    };
-    auto emit_tile = [&](const std::string &sfx, const std::string &itx) {
-      std::string o;
-      char bb[1024];
-      o += "      if (lane < FR) fm[wv][lane] = 0;\n"
-           "      {\n"
-           "      uint32_t pm = 0;\n"
-           "#pragma unroll\n"
-           "      for (uint32_t k = 0; k < FR; k++) {\n";
-      snprintf(bb, sizeof bb,
-               "        const uint32_t r = rt%s + k;\n"
-               "        bool live = r < rend;\n",
-               sfx.c_str());
-      o += bb;
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 1) {
-          if (st.leaf_multi[i])
-            snprintf(bb, sizeof bb,
-                     "        if (live && !l%d_all) {\n"
-                     "          uint64_t v = ((wl%d%s >> (k * l%dW)) & "
-                     "lmk%d) ^ lb%d.mask;\n"
-                     "          live = ((v - lb%d.lo) <= (lb%d.hi - "
-                     "lb%d.lo)) != (bool)lb%d.invert;\n"
-                     "        }\n",
-                     i, i, sfx.c_str(), i, i, i, i, i, i, i);
-          else
-            snprintf(bb, sizeof bb,
-                     "        if (live && !l%d_all) {\n"
-                     "          uint64_t v = jit_bread(bp, l%do + r * "
-                     "l%dW, l%dW) ^ lb%d.mask;\n"
-                     "          live = ((v - lb%d.lo) <= (lb%d.hi - "
-                     "lb%d.lo)) != (bool)lb%d.invert;\n"
-                     "        }\n",
-                     i, i, i, i, i, i, i, i, i);
-        } else {
-          if (st.leaf_multi[i])
-            snprintf(bb, sizeof bb,
-                     "        if (live)\n"
-                     "          live = (lb%d.mask >>\n"
-                     "                  (uint32_t)((wl%d%s >> (k * l%dW)) "
-                     "& lmk%d)) & 1;\n",
-                     i, i, sfx.c_str(), i, i);
-          else
-            snprintf(bb, sizeof bb,
-                     "        if (live)\n"
-                     "          live = (lb%d.mask >>\n"
-                     "                  (uint32_t)jit_bread(bp, l%do + r "
-                     "* l%dW, l%dW)) & 1;\n",
-                     i, i, i, i);
-        }
-        o += bb;
-      }
-      if (st.fprobe == 2) {
-        /* loads-only probe: defeat DCE by folding the words into
-           lane_cnt; measures the achievable thin-stream read rate */
-        o += "        pm |= live ? (1u << k) : 0u;\n"
-             "      }\n";
-        for (int i = 0; i < NL; i++)
-          if (st.leaf_multi[i]) {
-            snprintf(bb, sizeof bb,
-                     "      lane_cnt += (uint32_t)(wl%d%s ^ (wl%d%s >> "
-                     "32));\n",
-                     i, sfx.c_str(), i, sfx.c_str());
-            o += bb;
-          }
-        o += "      lane_cnt += pm;\n"
-             "      }\n";
-        return o;
-      }
-      snprintf(bb, sizeof bb,
-               "        pm |= live ? (1u << k) : 0u;\n"
-               "      }\n"
-               "      lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
-               "      /* wave-synchronous LDS mask assembly: DS ops of one\n"
-               "         wave execute in program order (lockstep wave64), "
-               "so\n"
-               "         the read below sees every lane's OR, barrier-free "
-               "*/\n"
-               "      if (pm)\n"
-               "        atomicOr(&fm[wv][lane >> %d],\n"
-               "                 (unsigned long long)pm << ((lane & %uu) * "
-               "FR));\n"
-               "      if (lane < FR) {\n"
-               "        unsigned long long m = fm[wv][lane];\n"
-               "        if (m) {\n"
-               "          const uint64_t pos =\n"
-               "              row0 + (uint64_t)(%s) * (64 * FR) + lane * "
-               "64;\n"
-               "          const uint64_t w0 = pos >> 6;\n"
-               "          const uint32_t sh = (uint32_t)(pos & 63);\n"
-               "          atomicOr(&bitmap[w0], m << sh);\n"
-               "          if (sh && (m >> (64 - sh)))\n"
-               "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
-               "        }\n"
-               "      }\n"
-               "      }\n",
-               R == 4 ? 4 : 5, R == 4 ? 15u : 31u, itx.c_str());
-      if (st.fprobe == 1) { /* no-flush probe: eval but skip bitmap */
-        o += "        pm |= live ? (1u << k) : 0u;\n"
-             "      }\n"
-             "      lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
-             "      }\n";
-        return o;
-      }
-      o += bb;
-      return o;
-    };
-    s += "    const uint32_t nr = rend - rbeg;\n"
-         "    const uint32_t iters = (nr + 64 * FR - 1) / (64 * FR);\n"
-         "    uint32_t it = 0;\n";
-    if (FU > 1) {
-      snprintf(b, sizeof b, "    for (; it + %d <= iters; it += %d) {\n",
-               FU, FU);
-      s += b;
-      for (int u = 0; u < FU; u++) {
-        char sfx[8], itx[16];
-        snprintf(sfx, sizeof sfx, "_%d", u);
-        snprintf(itx, sizeof itx, "it + %d", u);
-        s += emit_pre(sfx, itx);
-      }
-      for (int u = 0; u < FU; u++) {
-        char sfx[8], itx[16];
-        snprintf(sfx, sizeof sfx, "_%d", u);
-        snprintf(itx, sizeof itx, "it + %d", u);
-        s += emit_tile(sfx, itx);
-      }
-      s += "    }\n";
-    }
-    s += "    for (; it < iters; it++) {\n";
-    s += emit_pre("", "it");
-    s += emit_tile("", "it");
-    s += "    }\n"
-         "  }\n";
-  } else {
-  s += "    const uint32_t nr = rend - rbeg;\n"
-       "    const uint32_t iters = (nr + 63) / 64;\n"
-       "    for (uint32_t it = 0; it < iters; it++) {\n"
-       "      const uint32_t r = rbeg + it * 64 + lane;\n"
-       "      bool live = r < rend;\n";
-  for (int i = 0; i < NL; i++) {
-    if (st.leaf_kind[i] == 1) {
-      snprintf(b, sizeof b,
-               "      if (live && !l%d_all) {\n"
-               "        uint64_t v = jit_bread(bp, l%do + r * l%dW, l%dW) ^ "
-               "lb%d.mask;\n"
-               "        live = ((v - lb%d.lo) <= (lb%d.hi - lb%d.lo)) != "
-               "(bool)lb%d.invert;\n"
-               "      }\n",
-               i, i, i, i, i, i, i, i, i);
-    } else {
-      snprintf(b, sizeof b,
-               "      if (live)\n"
-               "        live = (lb%d.mask >>\n"
-               "                (uint32_t)jit_bread(bp, l%do + r * l%dW, "
-               "l%dW)) & 1;\n",
-               i, i, i, i);
-    }
-    s += b;
-  }
-  s += "      uint64_t m = __ballot(live);\n"
-       "      lane_cnt += live ? 1u : 0u;\n"
-       "      if (lane == 0 && m) {\n"
-       "        const uint64_t pos = row0 + (uint64_t)it * 64;\n"
-       "        const uint64_t w0 = pos >> 6;\n"
-       "        const uint32_t sh = (uint32_t)(pos & 63);\n"
-       "        atomicOr(&bitmap[w0], m << sh);\n"
-       "        if (sh && (m >> (64 - sh)))\n"
-       "          atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
-       "      }\n"
-       "    }\n"
-       "  }\n";
-  }
-  s += "  for (int off = 32; off > 0; off >>= 1)\n"
-       "    lane_cnt += (uint32_t)__shfl_xor((int)lane_cnt, off, 64);\n"
-       "  __syncthreads();\n"
-       "  if (lane == 0 && lane_cnt)\n"
-       "    atomicAdd(&wsum, (unsigned long long)lane_cnt);\n"
-       "  __syncthreads();\n"
-       "  if (tid == 0 && wsum)\n"
-       "    atomicAdd(&counters[8 + (blockIdx.x & 7)], wsum);\n"
-       "}\n";
-  return s;
-}
-
-/* compile-or-fetch for the filter kernel */
-static jit_entry *jit_get_filter(const dev_plan_hdr &ph,
-                                 const jit_strategy &st) {
-  std::string key = jit_fstrategy_sig(ph, st);
-  auto it = g_jit_cache.find(key);
-  if (it != g_jit_cache.end())
-    return it->second.fn ? &it->second : nullptr;
-  jit_entry ent;
-  std::string src = jit_gen_source_filter(ph, st);
-  if (getenv("OBX_JIT_DUMP")) {
-    FILE *f = fopen("gpurun_out/obx_jit_filter_src.hip", "w");
-    if (!f) f = fopen("/tmp/obx_jit_filter_src.hip", "w");
-    if (f) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
-  }
-  hiprtcProgram prog;
-  const char *hdrs[2] = {OBX_JIT_SRC_COMMON_H, OBX_JIT_SRC_DEV_H};
-  const char *hdr_names[2] = {"obx_dev_common.h", "obx_dev.h"};
-  if (hiprtcCreateProgram(&prog, src.c_str(), "obx_jit_filter.hip", 2, hdrs,
-                          hdr_names) != HIPRTC_SUCCESS) {
-    g_jit_cache[key] = ent;
-    return nullptr;
-  }
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-                        "-DOBX_HIPRTC=1"};
-  if (hiprtcCompileProgram(prog, 4, opts) != HIPRTC_SUCCESS) {
-    size_t lsz = 0;
-    hiprtcGetProgramLogSize(prog, &lsz);
-    if (lsz > 1) {
-      std::string log(lsz, '\0');
-      hiprtcGetProgramLog(prog, &log[0]);
-      fprintf(stderr, "obx: filter JIT compile failed:\n%s\n", log.c_str());
-    }
-    hiprtcDestroyProgram(&prog);
-    g_jit_cache[key] = ent;
-    return nullptr;
-  }
-  size_t csz = 0;
-  hiprtcGetCodeSize(prog, &csz);
-  std::string code(csz, '\0');
-  hiprtcGetCode(prog, &code[0]);
-  hiprtcDestroyProgram(&prog);
-  if (hipModuleLoadData(&ent.mod, code.data()) != hipSuccess ||
-      hipModuleGetFunction(&ent.fn, ent.mod, "k_jit_filter") != hipSuccess) {
-    ent.fn = nullptr;
-    g_jit_cache[key] = ent;
-    return nullptr;
-  }
-  auto r = g_jit_cache.emplace(key, ent);
-  return &r.first->second;
-}
-
-static jit_entry *jit_prepare_filter(const obx_handle &h,
-                                     const dev_plan_hdr &ph,
-                                     const dev_leaf *pl, int want_row_ids) {
-  const char *e = getenv("OBX_JIT");
-  if (e && e[0] == '0') return nullptr;
-  jit_strategy st;
-  if (!jit_build_fstrategy(h, ph, pl, st)) return nullptr;
-  if (want_row_ids) {
-    /* ordered selection vectors need the per-block mask capture of the
-       staged kernel and a bounded chunk count for the LDS mask array */
-    uint32_t nch = ((h.max_block_rows ? h.max_block_rows : 4096) + 63) / 64;
-    if (!st.fstage || st.fprobe || nch > 256) return nullptr;
-    st.frid = 1;
-    st.fnch = (uint16_t)nch;
-  }
-  return jit_get_filter(ph, st);
 }
