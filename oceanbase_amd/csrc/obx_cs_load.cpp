@@ -29,33 +29,19 @@
  * stream-offset stream and dict ref streams are RAW-encoded; the string
  * pool is uncompressed.
  */
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
 #include <cstring>
-#include <vector>
 
 #include "obx_cs_dev.h"
-#include "obx_dev.h"
-
-#ifndef OBX_WG_HOST
-#define OBX_WG_HOST 256
-#endif
-#include "../../include/obx.h"
-#include "../../oracle/obx_format.h"
+#include "obx_host.h"
 
 extern "C" __global__ void k_cs_decode(const uint8_t *, const cs_dev_stream *,
                                        uint32_t, uint8_t *);
 
-/* from obx_engine.cpp */
-struct obx_gpu_ctx;
-struct obx_handle;
-int obx_cs_finish_load(obx_gpu_ctx *ctx, obx_handle *h,
-                       const obx_col_schema *cols, uint16_t n_cols,
-                       std::vector<dev_block> &blocks, uint8_t *d_buf,
-                       uint64_t arena_bytes, uint64_t total_rows);
-int obx_cs_alloc_handle(obx_gpu_ctx *ctx, obx_handle **h_out);
-int obx_cs_publish_handle(obx_gpu_ctx *ctx, obx_handle *h);
+/* what the host half leaves for the device: the decode tasks of the two
+   phases (p1: source -> scratch / arena, p2: scratch -> arena) */
+struct obx_cs_plan {
+  std::vector<cs_dev_stream> p1, p2;
+};
 
 namespace {
 
@@ -349,9 +335,14 @@ static int parse_cs_block(const uint8_t *buf, size_t len, uint64_t src_base,
 
 /* ---- arena planning + the load entry point ----------------------------- */
 
-extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
-                                      const obx_blockset *bs) {
-  if (!ctx || !bs || !bs->data || !bs->cols) return OBX_INVALID_ARGUMENT;
+/* host half: parse every block, plan the arena (h.total_bytes) and the
+   decode tasks, and fold each chunk's descriptor into h's facts */
+int obx_cs_host_load(const obx_blockset *bs, obx_handle &h,
+                     std::vector<dev_block> &blocks, obx_cs_plan *plan) {
+  if (!bs->data || !bs->cols) return OBX_INVALID_ARGUMENT;
+  obx_cs_plan facts_only;
+  if (!plan) plan = &facts_only;
+  std::vector<cs_dev_stream> &p1 = plan->p1, &p2 = plan->p2;
   const uint16_t n_cols = bs->n_cols;
   if (n_cols == 0 || n_cols > OBX_DEV_MAX_COLS) return OBX_NOT_SUPPORTED;
   for (uint16_t c = 0; c < n_cols; c++) {
@@ -364,22 +355,14 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
     }
   }
 
-  /* pass 1: parse every block, plan arena + scratch + stream tasks */
-  struct chunk_plan {
-    dev_block db;
-  };
-  std::vector<dev_block> blocks;
-  std::vector<cs_dev_stream> p1, p2;
+  h.n_cols = n_cols;
+  memcpy(h.cols, bs->cols, sizeof(obx_col_schema) * n_cols);
   uint64_t arena = 0;   /* chunk region cursor */
-  uint64_t total_rows = 0;
-  const uint64_t src_total = bs->block_offsets[bs->n_blocks];
 
-  /* scratch tail starts after all chunks — two-pass: first compute chunk
-     bytes, then assign scratch; simpler: collect tasks with scratch
-     offsets relative to a scratch cursor, fix up after */
-  uint64_t scratch = 0; /* relative cursor; rebased later */
-  struct fixup { size_t idx; int which; }; /* which: 1 src_byte, 2 out_byte */
-  std::vector<fixup> fx1, fx2;
+  /* the scratch tail starts after all chunks: tasks carry scratch offsets
+     relative to a scratch cursor, rebased once the chunk bytes are known */
+  uint64_t scratch = 0;
+  std::vector<size_t> fx1, fx2; /* p2 tasks' src_byte, p1 tasks' out_byte */
   auto scratch_alloc = [&](uint64_t bytes) {
     uint64_t off = scratch;
     scratch += (bytes + 15) & ~15ull;
@@ -410,7 +393,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
         s.op = OBX_CSOP_INT64;
         s.enc_type = p.im.type;
         s.wb = (uint8_t)WB[p.im.width_tag & 3];
-        fx2.push_back({p1.size(), 2});
+        fx2.push_back(p1.size());
         s.out_byte = sc_vals[c];
         p1.push_back(s);
       } else if ((p.h.type == CT_IDICT || p.h.type == CT_SDICT) &&
@@ -425,7 +408,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
           s.op = OBX_CSOP_INT64;
           s.enc_type = p.im.type;
           s.wb = (uint8_t)WB[p.im.width_tag & 3];
-          fx2.push_back({p1.size(), 2});
+          fx2.push_back(p1.size());
           s.out_byte = sc_ent[c];
           p1.push_back(s);
         }
@@ -439,7 +422,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
         s.op = OBX_CSOP_INT64;
         s.enc_type = p.rm.type;
         s.wb = (uint8_t)WB[p.rm.width_tag & 3];
-        fx2.push_back({p1.size(), 2});
+        fx2.push_back(p1.size());
         s.out_byte = sc_refs[c];
         p1.push_back(s);
       }
@@ -486,8 +469,8 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
       const uint64_t cbase = arena; /* 16-aligned below */
       uint64_t off = 0;             /* within chunk */
       dev_block db{};
-      db.row_start_lo = (uint32_t)(total_rows + r0);
-      db.row_start_hi = (uint32_t)((total_rows + r0) >> 32);
+      db.row_start_lo = (uint32_t)h.total_rows; /* rows folded so far */
+      db.row_start_hi = (uint32_t)(h.total_rows >> 32);
       db.row_count = n;
       db.block_byte = cbase;
       for (uint16_t c = 0; c < n_cols; c++) {
@@ -514,7 +497,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
                 s.op = OBX_CSOP_EXT_REPLACE;
                 s.base = (int64_t)p.im.null_replaced;
                 s.src_byte = sc_vals[c] + (uint64_t)r0 * 8;
-                fx1.push_back({p2.size(), 1});
+                fx1.push_back(p2.size());
                 p2.push_back(s);
               } else {
                 s.op = OBX_CSOP_EXT_BITMAP;
@@ -532,7 +515,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
               s.wb = 8;
               s.src_byte = sc_vals[c] + (uint64_t)r0 * 8;
               s.out_byte = cbase + off;
-              fx1.push_back({p2.size(), 1});
+              fx1.push_back(p2.size());
               p2.push_back(s);
             }
             off += (uint64_t)n * 8;
@@ -587,7 +570,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
               s.wb = 8;
               s.src_byte = sc_ent[c];
               s.out_byte = cbase + off;
-              fx1.push_back({p2.size(), 1});
+              fx1.push_back(p2.size());
               p2.push_back(s);
             } else {
               cs_dev_stream s{};
@@ -612,7 +595,7 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
                 s.op = OBX_CSOP_REFS;
                 s.src_byte = sc_refs[c] + (uint64_t)r0 * 8;
               }
-              fx1.push_back({p2.size(), 1});
+              fx1.push_back(p2.size());
               p2.push_back(s);
             }
             off += (uint64_t)n * rw;
@@ -623,63 +606,66 @@ extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
       }
       db.block_len = (uint32_t)off;
       blocks.push_back(db);
+      obx_fold_block(h, db);
       arena += (off + 15) & ~15ull;
     }
-    total_rows += rows;
   }
 
   /* rebase scratch offsets to the arena tail */
   const uint64_t scratch_base = (arena + 63) & ~63ull;
-  const uint64_t arena_total = scratch_base + scratch + 64;
-  for (auto &f : fx1) p2[f.idx].src_byte += scratch_base;
-  for (auto &f : fx2) p1[f.idx].out_byte += scratch_base;
+  h.total_bytes = scratch_base + scratch + 64;
+  for (size_t i : fx1) p2[i].src_byte += scratch_base;
+  for (size_t i : fx2) p1[i].out_byte += scratch_base;
+  /* dict payloads live only on the device for CS handles; the persistent
+     JIT path requires the host-verified byte-identical dicts, so it is
+     simply not taken (col_dict_stable stays false -> v1 JIT / generic
+     kernels, which are parity-equal) */
+  return OBX_SUCCESS;
+}
 
-  /* device: upload src + tasks, decode in two phases into the arena */
-  obx_handle *h = nullptr;
-  int rc = obx_cs_alloc_handle(ctx, &h);
-  if (rc != OBX_SUCCESS) return rc;
-  uint8_t *d_src = nullptr, *d_buf = nullptr;
-  cs_dev_stream *d_ss = nullptr;
-  auto fail = [&](int code) {
-    (void)hipFree(d_src);
-    (void)hipFree(d_ss);
-    (void)hipFree(d_buf);
-    return code;
-  };
-  if (hipMalloc(&d_buf, arena_total) != hipSuccess)
-    return fail(OBX_INTERNAL_ERROR);
-  if (hipMalloc(&d_src, src_total + 64) != hipSuccess)
-    return fail(OBX_INTERNAL_ERROR);
-  if (hipMemcpy(d_src, bs->data, src_total, hipMemcpyHostToDevice) !=
-      hipSuccess)
-    return fail(OBX_INTERNAL_ERROR);
-  size_t n1 = p1.size(), n2 = p2.size();
-  if (hipMalloc(&d_ss, (n1 + n2) * sizeof(cs_dev_stream)) != hipSuccess)
-    return fail(OBX_INTERNAL_ERROR);
+/* arena upload: stage the source bytes + tasks and decode in two phases
+   into h.d_buf; the staging is gone when this returns */
+static int cs_decode_arena(const obx_blockset *bs, const obx_cs_plan &plan,
+                           obx_handle &h) {
+  const uint64_t src_total = bs->block_offsets[bs->n_blocks];
+  const size_t n1 = plan.p1.size(), n2 = plan.p2.size();
+  dev_tmp<uint8_t> src;
+  dev_tmp<cs_dev_stream> ss;
+  HIP_TRY(hipMalloc(&h.d_buf, h.total_bytes));
+  HIP_TRY(hipMalloc(&src.p, src_total + 64));
+  HIP_TRY(hipMemcpy(src.p, bs->data, src_total, hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&ss.p, (n1 + n2) * sizeof(cs_dev_stream)));
   if (n1)
-    (void)hipMemcpy(d_ss, p1.data(), n1 * sizeof(cs_dev_stream),
-                    hipMemcpyHostToDevice);
+    HIP_TRY(hipMemcpy(ss.p, plan.p1.data(), n1 * sizeof(cs_dev_stream),
+                      hipMemcpyHostToDevice));
   if (n2)
-    (void)hipMemcpy(d_ss + n1, p2.data(), n2 * sizeof(cs_dev_stream),
-                    hipMemcpyHostToDevice);
+    HIP_TRY(hipMemcpy(ss.p + n1, plan.p2.data(), n2 * sizeof(cs_dev_stream),
+                      hipMemcpyHostToDevice));
   auto grid = [&](size_t n) {
     uint32_t waves = (uint32_t)((n + 3) / 4);
     return waves < 4096 ? (waves ? waves : 1) : 4096;
   };
   if (n1)
     hipLaunchKernelGGL(k_cs_decode, dim3(grid(n1)), dim3(256), 0, nullptr,
-                       d_src, d_ss, (uint32_t)n1, d_buf);
+                       src.p, ss.p, (uint32_t)n1, h.d_buf);
   if (n2)
     hipLaunchKernelGGL(k_cs_decode, dim3(grid(n2)), dim3(256), 0, nullptr,
-                       d_src, d_ss + n1, (uint32_t)n2, d_buf);
-  if (hipDeviceSynchronize() != hipSuccess) return fail(OBX_INTERNAL_ERROR);
-  (void)hipFree(d_src);
-  (void)hipFree(d_ss);
-  d_src = nullptr;
-  d_ss = nullptr;
-
-  rc = obx_cs_finish_load(ctx, h, bs->cols, n_cols, blocks, d_buf,
-                          arena_total, total_rows);
-  if (rc != OBX_SUCCESS) return fail(rc);
-  return obx_cs_publish_handle(ctx, h);
+                       src.p, ss.p + n1, (uint32_t)n2, h.d_buf);
+  HIP_TRY(hipDeviceSynchronize());
+  return OBX_SUCCESS;
 }
+
+extern "C" int obx_gpu_load_cs_blocks(obx_gpu_ctx *ctx,
+                                      const obx_blockset *bs) {
+  if (!ctx || !bs) return OBX_INVALID_ARGUMENT;
+  auto h = std::make_unique<obx_handle>();
+  std::vector<dev_block> blocks;
+  obx_cs_plan plan;
+  int rc = obx_cs_host_load(bs, *h, blocks, &plan);
+  if (rc != OBX_SUCCESS) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = cs_decode_arena(bs, plan, *h);
+  if (rc != OBX_SUCCESS) return rc;
+  return obx_finish_load(ctx, std::move(h), blocks);
+}
+

@@ -12,184 +12,11 @@
  * This is the PRODUCT path: it fails loudly (OBX_NO_GPU) when no HIP device
  * is present — it never falls back to the CPU oracle.
  */
-#include <hip/hip_runtime.h>
-
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <vector>
 #include <algorithm>
 
-#include "obx_dev.h"
-
-#ifndef OBX_WG_HOST
-#define OBX_WG_HOST 256  /* must match the kernels' WG */
-#endif
-#include "../../include/obx.h"
-#include "../../oracle/obx_format.h"
-
-/* kernels (obx_kernels.hip) */
-extern "C" __global__ void k_decode_lds(
-    const uint8_t *, const dev_block *, uint32_t, uint32_t, uint32_t,
-    uint8_t *, uint8_t *);
-extern "C" __global__ void k_decode_multi(
-    const uint8_t *, const dev_block *, uint32_t, const uint16_t *,
-    const uint8_t *, uint32_t, uint8_t *const *, uint8_t *const *);
-extern "C" __global__ void k_scan_agg_direct(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
-extern "C" __global__ void k_scan_filter_agg(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
-extern "C" __global__ void k_scan_filter_agg_lds(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
-extern "C" __global__ void k_filter(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
-    unsigned long long *);
-extern "C" __global__ void k_filter_lds(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
-    unsigned long long *);
-/* _prog variants: compiled with the postfix AND/OR combine-program path
-   (reference: ObPushdownFilterExecutor AND/OR trees); separate entry points
-   so the AND-only fast path keeps its lean register budget. */
-extern "C" __global__ void k_scan_filter_agg_prog(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
-extern "C" __global__ void k_scan_filter_agg_prog_lds(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
-extern "C" __global__ void k_filter_prog(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
-    unsigned long long *);
-extern "C" __global__ void k_filter_prog_lds(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
-    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
-    unsigned long long *);
-extern "C" __global__ void k_decode(
-    const uint8_t *, const dev_block *, uint32_t, uint32_t, uint32_t,
-    uint8_t *, uint8_t *);
-extern "C" __global__ void k_group_pass(
-    const uint8_t *, const dev_block *, uint32_t, const dev_plan_hdr,
-    const uint64_t *, uint8_t *, gslot *, unsigned long long *);
-extern "C" __global__ void k_agg_pass(
-    const uint8_t *, const dev_block *, uint32_t, const dev_plan_hdr,
-    uint32_t, const uint64_t *, const uint8_t *, gslot *);
-extern "C" __global__ void k_lower_leaves(
-    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *, uint32_t,
-    uint32_t, const int64_t *, blk_leaf *);
-extern "C" __global__ void k_col_minmax(
-    const uint8_t *, const dev_block *, uint32_t, uint32_t, int64_t *);
-extern "C" __global__ void k_gtable_init(
-    unsigned long long *, uint32_t, uint32_t, uint32_t, uint32_t);
-
-#define HIP_TRY(x)                                        \
-  do {                                                    \
-    hipError_t _e = (x);                                  \
-    if (_e != hipSuccess) {                               \
-      fprintf(stderr, "obx: HIP error %s at %s:%d\n",     \
-              hipGetErrorString(_e), __FILE__, __LINE__); \
-      return OBX_INTERNAL_ERROR;                          \
-    }                                                     \
-  } while (0)
-
-#include <cstdio>
-
-struct obx_handle {
-  uint8_t *d_buf = nullptr;
-  dev_block *d_blocks = nullptr;
-  uint32_t n_blocks = 0;
-  uint16_t n_cols = 0;
-  uint64_t total_rows = 0;
-  uint64_t total_bytes = 0;
-  obx_col_schema cols[OBX_DEV_MAX_COLS];
-  /* query scratch */
-  blk_leaf *d_bleaves = nullptr;
-  uint32_t bleaves_cap = 0; /* in (block,leaf) entries */
-  dev_leaf *d_pleaves = nullptr;
-  gslot *d_gtable = nullptr;
-  unsigned long long *d_counters = nullptr;
-  uint64_t *d_bitmap = nullptr;
-  int32_t *d_row_ids = nullptr;
-  uint32_t *d_blk_counts = nullptr;
-  uint8_t *d_row_slot = nullptr;
-  uint8_t *d_decode_out[OBX_DEV_MAX_COLS] = {};
-  uint64_t last_survivors = 0;
-  gslot *d_gtable_big = nullptr; /* high-cardinality direct kernel table */
-  void *d_proj_scratch = nullptr; /* k_decode_multi proj/len/out arrays */
-  std::vector<obx_group_row> last_rows; /* full sorted group rows of the
-                                           last scan (obx_gpu_agg_fetch) */
-  bool lds_ok = false;   /* all blocks 16-B aligned and <= LDS stage size */
-  bool in_use = false;
-  /* per-(block,col) encoding summary captured at load time for the JIT
-     eligibility walk (obx_jit.inc): low nibble = decode class (0 raw,
-     1 dict, 2 intdiff, 3 const, 4 slow), bit4 = string; col_cnt = dict
-     count capped at 255 */
-  std::vector<uint8_t> col_class, col_cnt;
-  /* per-column folds of col_class / col_cnt (summarize_col_classes, at
-     load): everything the per-query plan and JIT eligibility tests ask of
-     the per-block arrays, so a query costs O(columns), not O(blocks) */
-  bool col_span_any[OBX_DEV_MAX_COLS] = {};    /* class 5 in any block */
-  bool col_grp16_every[OBX_DEV_MAX_COLS] = {}; /* class 1 and count < 16 in
-                                                  every block */
-  bool col_slow_any[OBX_DEV_MAX_COLS] = {};    /* class > 3 or string in
-                                                  any block */
-  uint32_t col_cnt_max[OBX_DEV_MAX_COLS] = {}; /* max of col_cnt */
-  /* max over blocks of (cnt[c0]+1)*(cnt[c1]+1), filled on the first query
-     that groups by (c0, c1) and whose product of column maxima exceeds the
-     16-cell limit (key = c0 << 16 | c1) */
-  mutable std::map<uint32_t, uint32_t> pair_cells_max;
-  uint32_t n_cus = 256; /* compute units of the owning device */
-  /* stored skip index: per-(block,col) [min,max] of non-null decoded
-     values, captured by k_col_minmax at load (device copy feeds
-     k_lower_leaves pruning; host summary feeds the JIT's i64-accumulator
-     range eligibility, obx_jit.inc) */
-  int64_t *d_minmax = nullptr;
-  int64_t col_min[OBX_DEV_MAX_COLS] = {};   /* global over blocks */
-  int64_t col_max[OBX_DEV_MAX_COLS] = {};
-  bool col_known[OBX_DEV_MAX_COLS] = {};    /* bounds known in EVERY block */
-  bool col_dict_every[OBX_DEV_MAX_COLS] = {}; /* class==1 and count<=63
-                                                 in every block */
-  bool col_dict_any[OBX_DEV_MAX_COLS] = {};   /* dict (incl. char) with
-                                                 count<=63 in every block */
-  bool col_dict_stable[OBX_DEV_MAX_COLS] = {}; /* dict_any AND the dict
-                                                  payload is byte-identical
-                                                  in every block (group/ref
-                                                  persistence; numeric-only
-                                                  uses additionally require
-                                                  col_dict_every) */
-  bool col_ext_any[OBX_DEV_MAX_COLS] = {};  /* HAS_EXT in any block */
-  bool col_raw8_every[OBX_DEV_MAX_COLS] = {}; /* 8-B RAW, 64-bit-aligned,
-                                                 no ext, in every block */
-  bool col_rangefam_every[OBX_DEV_MAX_COLS] = {}; /* RAW numeric / INTDIFF
-                                                     (packed-range lowerable)
-                                                     in every block */
-  uint32_t col_maxcnt[OBX_DEV_MAX_COLS] = {}; /* max dict count */
-  uint32_t col_maxw[OBX_DEV_MAX_COLS] = {};   /* max packed width (bits)
-                                                 across blocks; 255 = no
-                                                 packed stream (slow enc) */
-  uint32_t max_block_rows = 0;
-  uint32_t max_block_len = 0;
-};
-
-struct obx_gpu_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
-  double last_ms = 0.0;
-  double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
-  int last_jit = 0;           /* last scan used the specialized kernel */
-  uint32_t last_grid = 0;     /* workgroups that kernel was launched with */
-  uint32_t n_cus = 256;
-  /* pinned landing buffer for the group table + counters of a scan (sized
-     for the growth-path table) */
-  uint8_t *h_result = nullptr;
-  std::vector<obx_handle> handles;
-};
+#include "obx_host.h"
 
 /* device words after the group table that hold the 16 scan counters: one
    allocation, so one copy fetches both */
@@ -222,20 +49,33 @@ extern "C" int obx_gpu_open(int device, obx_gpu_ctx **out) {
 extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   if (!ctx) return OBX_SUCCESS;
   (void)hipSetDevice(ctx->device);
-  for (auto &h : ctx->handles) {
-    if (!h.in_use) continue;
-    (void)hipFree(h.d_buf); (void)hipFree(h.d_blocks); (void)hipFree(h.d_bleaves);
-    (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
-    (void)hipFree(h.d_bitmap); (void)hipFree(h.d_row_ids); (void)hipFree(h.d_blk_counts);
-    (void)hipFree(h.d_row_slot); (void)hipFree(h.d_minmax);
-    for (auto *p : h.d_decode_out) (void)hipFree(p);
-  }
+  ctx->handles.clear(); /* ~obx_handle, while the device is current */
   (void)hipStreamDestroy(ctx->stream);
-  (void)hipEventDestroy(ctx->ev_start);
-  (void)hipEventDestroy(ctx->ev_stop);
+  for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1})
+    (void)hipEventDestroy(ev);
   (void)hipHostFree(ctx->h_result);
   delete ctx;
   return OBX_SUCCESS;
+}
+
+/* the one place a handle's device memory is released (d_counters is the
+   tail of d_gtable). Never-loaded handles, as the GPU-free probes build
+   them, hold only nulls and make no HIP call. */
+obx_handle::~obx_handle() {
+  void *owned[] = {d_buf, d_blocks, d_bleaves, d_pleaves, d_gtable,
+                   d_gtable_big, d_proj_scratch, d_bitmap, d_row_ids,
+                   d_blk_counts, d_row_slot, d_minmax};
+  for (void *p : owned)
+    if (p) (void)hipFree(p);
+  for (uint8_t *p : d_decode_out)
+    if (p) (void)hipFree(p);
+}
+
+/* every verb resolves its handle id here: null for a null context, an id
+   out of range, or a freed handle */
+static obx_handle *lookup(obx_gpu_ctx *ctx, int handle) {
+  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size()) return nullptr;
+  return ctx->handles[handle].get();
 }
 
 /* Load-time payload checksum (the reference verifies data_checksum_ when a
@@ -254,11 +94,6 @@ static uint64_t host_crc32c(const uint8_t *buf, int64_t len) {
   }
   for (; i < len; i++) crc = __builtin_ia32_crc32qi((uint32_t)crc, buf[i]);
   return crc;
-}
-
-static uint32_t grid_for(uint32_t n_blocks) {
-  uint32_t g = n_blocks < 4096u ? n_blocks : 4096u;
-  return g ? g : 1;
 }
 
 /* grid of the persistent scan JIT (obx_jit_scan.inc): OBX_JIT_GRID_WAVES
@@ -291,28 +126,74 @@ static void gtable_init(gslot *gt, uint32_t n_slots, uint32_t tail_words,
                      n_slots, tail_words, min_mask, max_mask);
 }
 
-/* fold the per-(block,col) class/count arrays into the per-column facts
-   build_plan and jit_blocks_ok test; every loader calls this once */
+/* fold the newest block's row of col_class / col_cnt into the per-column
+   facts build_plan and jit_blocks_ok test. obx_fold_block appends that row
+   from a parsed block; the GPU-free probes append synthetic ones. */
 static void summarize_col_classes(obx_handle &h) {
   const uint32_t nc = h.n_cols;
+  const bool first = h.col_class.size() == nc;
+  const uint8_t *cls = h.col_class.data() + h.col_class.size() - nc;
+  const uint8_t *cnt = h.col_cnt.data() + h.col_cnt.size() - nc;
   for (uint32_t c = 0; c < nc; c++) {
-    h.col_span_any[c] = h.col_slow_any[c] = false;
-    h.col_grp16_every[c] = true;
-    h.col_cnt_max[c] = 0;
+    const uint8_t k = cls[c];
+    if (first) h.col_grp16_every[c] = true;
+    if ((k & 0xF) == 5) h.col_span_any[c] = true;
+    if ((k & 0xF) != 1 || cnt[c] >= 16) h.col_grp16_every[c] = false;
+    if ((k & 0xF) > 3 || (k & 0x10)) h.col_slow_any[c] = true;
+    if (cnt[c] > h.col_cnt_max[c]) h.col_cnt_max[c] = cnt[c];
   }
-  h.pair_cells_max.clear();
-  const size_t nb = nc ? h.col_class.size() / nc : 0;
-  for (size_t b = 0; b < nb; b++) {
-    const uint8_t *cls = &h.col_class[b * nc];
-    const uint8_t *cnt = &h.col_cnt[b * nc];
-    for (uint32_t c = 0; c < nc; c++) {
-      const uint8_t k = cls[c];
-      if ((k & 0xF) == 5) h.col_span_any[c] = true;
-      if ((k & 0xF) != 1 || cnt[c] >= 16) h.col_grp16_every[c] = false;
-      if ((k & 0xF) > 3 || (k & 0x10)) h.col_slow_any[c] = true;
-      if (cnt[c] > h.col_cnt_max[c]) h.col_cnt_max[c] = cnt[c];
+}
+
+void obx_fold_block(obx_handle &h, const dev_block &db) {
+  const bool first = h.col_class.empty();
+  if ((db.block_byte & 15) ||
+      (uint64_t)db.block_len + 24 > OBX_LDS_STAGE_BYTES ||
+      db.row_count > 4096 /* OBX_MAX_BLOCK_ROWS */)
+    h.lds_ok = false;
+  for (uint16_t c = 0; c < h.n_cols; c++) {
+    const dev_col &dc = db.cols[c];
+    uint8_t cls;
+    switch (dc.enc) {
+      case OBX_D_RAW: cls = 0; break;
+      case OBX_D_DICT: cls = 1; break;
+      case OBX_D_INTDIFF: cls = 2; break;
+      case OBX_D_CONST: cls = dc.runs == 0 ? 3 : 4; break;
+      case OBX_D_EQUAL: case OBX_D_SUBSTR:
+        cls = 5; break; /* span: no device group keys */
+      default: cls = 4; break;
     }
+    if (dc.flags & OBX_DF_STRING) cls |= 0x10;
+    h.col_class.push_back(cls);
+    h.col_cnt.push_back((uint8_t)(dc.count > 254 ? 255 : dc.count));
+    if (first) {
+      h.col_dict_every[c] = true;
+      h.col_dict_any[c] = true;
+      h.col_raw8_every[c] = true;
+      h.col_rangefam_every[c] = true;
+    }
+    if ((cls & 0xF) != 1 || (cls & 0x10) || dc.count > 63)
+      h.col_dict_every[c] = false;
+    if ((cls & 0xF) != 1 || dc.count > 63)
+      h.col_dict_any[c] = false; /* dict (possibly char) everywhere */
+    if (!(dc.enc == OBX_D_RAW && !(dc.flags & OBX_DF_BITPACK) &&
+          !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT) &&
+          dc.width == 8 && (dc.data_bit & 63) == 0))
+      h.col_raw8_every[c] = false;
+    if (!((dc.enc == OBX_D_RAW || dc.enc == OBX_D_INTDIFF) &&
+          !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT)))
+      h.col_rangefam_every[c] = false;
+    if (dc.count > h.col_maxcnt[c]) h.col_maxcnt[c] = dc.count;
+    if (dc.flags & OBX_DF_HAS_EXT) h.col_ext_any[c] = true;
+    uint32_t w = 255; /* no packed stream: blocks multi-row reads */
+    if (dc.enc == OBX_D_RAW || dc.enc == OBX_D_DICT || dc.enc == OBX_D_INTDIFF)
+      w = (dc.flags & OBX_DF_BITPACK) ? dc.width : (uint32_t)dc.width * 8;
+    if (w > h.col_maxw[c]) h.col_maxw[c] = w;
   }
+  summarize_col_classes(h);
+  if (db.row_count > h.max_block_rows) h.max_block_rows = db.row_count;
+  if (db.block_len > h.max_block_len) h.max_block_len = db.block_len;
+  h.n_blocks++;
+  h.total_rows += db.row_count;
 }
 
 /* ---- host block parsing (mirrors ObMicroBlockDecoder pointer math,
@@ -544,8 +425,8 @@ static int parse_block(const obx_col_schema *cols, uint16_t n_cols,
   return OBX_SUCCESS;
 }
 
-extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
-  if (!ctx || !bs) return OBX_INVALID_ARGUMENT;
+int obx_pax_host_load(const obx_blockset *bs, obx_handle &h,
+                      std::vector<dev_block> &blocks) {
   if (bs->n_cols > OBX_DEV_MAX_COLS) return OBX_NOT_SUPPORTED;
   for (uint16_t c = 0; c < bs->n_cols; c++) {
     /* decimal scale bounds the P10 tables (reference: decimal-int
@@ -553,76 +434,18 @@ extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
     if (bs->cols[c].scale < 0 || bs->cols[c].scale > 18)
       return OBX_NOT_SUPPORTED;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
-  obx_handle h;
-  h.n_blocks = bs->n_blocks;
   h.n_cols = bs->n_cols;
   h.total_bytes = bs->block_offsets[bs->n_blocks];
   memcpy(h.cols, bs->cols, sizeof(obx_col_schema) * bs->n_cols);
-
-  std::vector<dev_block> blocks(bs->n_blocks);
-  uint64_t row_start = 0;
-  bool lds_ok = true;
+  blocks.resize(bs->n_blocks);
   for (uint32_t b = 0; b < bs->n_blocks; b++) {
-    uint64_t blen = bs->block_offsets[b + 1] - bs->block_offsets[b];
-    int rc = parse_block(bs->cols, bs->n_cols, bs->data + bs->block_offsets[b],
-                         bs->block_offsets[b], blen, row_start, &blocks[b]);
+    const uint64_t off = bs->block_offsets[b];
+    int rc = parse_block(bs->cols, bs->n_cols, bs->data + off, off,
+                         bs->block_offsets[b + 1] - off, h.total_rows,
+                         &blocks[b]);
     if (rc != OBX_SUCCESS) return rc;
-    if ((bs->block_offsets[b] & 15) || blen + 24 > OBX_LDS_STAGE_BYTES ||
-        blocks[b].row_count > 4096 /* OBX_MAX_BLOCK_ROWS */)
-      lds_ok = false;
-    for (uint16_t c = 0; c < bs->n_cols; c++) {
-      const dev_col &dc = blocks[b].cols[c];
-      uint8_t cls;
-      switch (dc.enc) {
-        case OBX_D_RAW: cls = 0; break;
-        case OBX_D_DICT: cls = 1; break;
-        case OBX_D_INTDIFF: cls = 2; break;
-        case OBX_D_CONST: cls = dc.runs == 0 ? 3 : 4; break;
-        case OBX_D_EQUAL: case OBX_D_SUBSTR:
-          cls = 5; break; /* span: no device group keys */
-        default: cls = 4; break;
-      }
-      if (dc.flags & OBX_DF_STRING) cls |= 0x10;
-      h.col_class.push_back(cls);
-      h.col_cnt.push_back((uint8_t)(dc.count > 254 ? 255 : dc.count));
-      if (b == 0) {
-        h.col_dict_every[c] = true;
-        h.col_dict_any[c] = true;
-        h.col_raw8_every[c] = true;
-        h.col_rangefam_every[c] = true;
-        h.col_maxcnt[c] = 0;
-      }
-      if ((cls & 0xF) != 1 || (cls & 0x10) || dc.count > 63)
-        h.col_dict_every[c] = false;
-      if ((cls & 0xF) != 1 || dc.count > 63)
-        h.col_dict_any[c] = false; /* dict (possibly char) everywhere */
-      if (!(dc.enc == OBX_D_RAW && !(dc.flags & OBX_DF_BITPACK) &&
-            !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT) &&
-            dc.width == 8 && (dc.data_bit & 63) == 0))
-        h.col_raw8_every[c] = false;
-      if (!((dc.enc == OBX_D_RAW || dc.enc == OBX_D_INTDIFF) &&
-            !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT)))
-        h.col_rangefam_every[c] = false;
-      if (dc.count > h.col_maxcnt[c]) h.col_maxcnt[c] = dc.count;
-      if (dc.flags & OBX_DF_HAS_EXT) h.col_ext_any[c] = true;
-      {
-        uint32_t w = 255; /* no packed stream: blocks multi-row reads */
-        if (dc.enc == OBX_D_RAW || dc.enc == OBX_D_DICT ||
-            dc.enc == OBX_D_INTDIFF)
-          w = (dc.flags & OBX_DF_BITPACK) ? dc.width : (uint32_t)dc.width * 8;
-        if (w > h.col_maxw[c]) h.col_maxw[c] = w;
-      }
-    }
-    if (blocks[b].row_count > h.max_block_rows)
-      h.max_block_rows = blocks[b].row_count;
-    if (blen > h.max_block_len) h.max_block_len = (uint32_t)blen;
-    row_start += blocks[b].row_count;
+    obx_fold_block(h, blocks[b]);
   }
-  h.total_rows = row_start;
-  h.lds_ok = lds_ok;
-  h.n_cus = ctx->n_cus;
-  summarize_col_classes(h);
   /* dict stability: identical dict payload in every block enables the
      JIT's persistent (whole-kernel) histograms/value tables */
   for (uint16_t c = 0; c < bs->n_cols; c++) {
@@ -637,63 +460,67 @@ extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
         h.col_dict_stable[c] = false;
     }
   }
+  return OBX_SUCCESS;
+}
 
-  HIP_TRY(hipMalloc(&h.d_buf, h.total_bytes + 64));
-  HIP_TRY(hipMemset(h.d_buf + h.total_bytes, 0, 64));
-  HIP_TRY(hipMemcpy(h.d_buf, bs->data, h.total_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h.d_blocks, sizeof(dev_block) * bs->n_blocks));
-  HIP_TRY(hipMemcpy(h.d_blocks, blocks.data(),
-                    sizeof(dev_block) * bs->n_blocks, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS)));
-  h.d_counters = (unsigned long long *)(h.d_gtable + OBX_GTABLE_SLOTS);
-  HIP_TRY(hipMalloc(&h.d_pleaves, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES));
+int obx_finish_load(obx_gpu_ctx *ctx, std::unique_ptr<obx_handle> h,
+                    const std::vector<dev_block> &blocks) {
+  h->n_cus = ctx->n_cus;
+  HIP_TRY(hipMalloc(&h->d_blocks, sizeof(dev_block) * blocks.size()));
+  HIP_TRY(hipMemcpy(h->d_blocks, blocks.data(),
+                    sizeof(dev_block) * blocks.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&h->d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS)));
+  h->d_counters = (unsigned long long *)(h->d_gtable + OBX_GTABLE_SLOTS);
+  HIP_TRY(hipMalloc(&h->d_pleaves, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES));
 
   /* stored skip index: capture per-(block,col) min/max once at load
      (k_col_minmax; outside every timed region) and summarize per column
      for the JIT's range eligibility */
-  {
-    uint64_t nmm = (uint64_t)bs->n_blocks * bs->n_cols * 2;
-    HIP_TRY(hipMalloc(&h.d_minmax, nmm * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_col_minmax, dim3(grid_for(bs->n_blocks)),
-                       dim3(OBX_WG_HOST), 0, nullptr, h.d_buf, h.d_blocks,
-                       bs->n_blocks, (uint32_t)bs->n_cols, h.d_minmax);
-    std::vector<int64_t> mm(nmm);
-    HIP_TRY(hipMemcpy(mm.data(), h.d_minmax, nmm * sizeof(int64_t),
-                      hipMemcpyDeviceToHost));
-    for (uint16_t c = 0; c < bs->n_cols; c++) {
-      int64_t gmin = INT64_MAX, gmax = INT64_MIN;
-      bool known = true;
-      for (uint32_t b = 0; b < bs->n_blocks; b++) {
-        int64_t mn = mm[2 * ((uint64_t)b * bs->n_cols + c)];
-        int64_t mx = mm[2 * ((uint64_t)b * bs->n_cols + c) + 1];
-        if (mn == INT64_MIN && mx == INT64_MAX) { known = false; break; }
-        if (mn <= mx) { /* empty (all-null) blocks don't widen */
-          if (mn < gmin) gmin = mn;
-          if (mx > gmax) gmax = mx;
-        }
+  const uint32_t nb = h->n_blocks, nc = h->n_cols;
+  const uint64_t nmm = (uint64_t)nb * nc * 2;
+  HIP_TRY(hipMalloc(&h->d_minmax, nmm * sizeof(int64_t)));
+  hipLaunchKernelGGL(k_col_minmax, dim3(grid_for(nb)), dim3(OBX_WG_HOST), 0,
+                     nullptr, h->d_buf, h->d_blocks, nb, nc, h->d_minmax);
+  std::vector<int64_t> mm(nmm);
+  HIP_TRY(hipMemcpy(mm.data(), h->d_minmax, nmm * sizeof(int64_t),
+                    hipMemcpyDeviceToHost));
+  for (uint32_t c = 0; c < nc; c++) {
+    int64_t gmin = INT64_MAX, gmax = INT64_MIN;
+    bool known = true;
+    for (uint32_t b = 0; b < nb; b++) {
+      int64_t mn = mm[2 * ((uint64_t)b * nc + c)];
+      int64_t mx = mm[2 * ((uint64_t)b * nc + c) + 1];
+      if (mn == INT64_MIN && mx == INT64_MAX) { known = false; break; }
+      if (mn <= mx) { /* empty (all-null) blocks don't widen */
+        if (mn < gmin) gmin = mn;
+        if (mx > gmax) gmax = mx;
       }
-      h.col_known[c] = known;
-      h.col_min[c] = gmin;
-      h.col_max[c] = gmax;
     }
+    h->col_known[c] = known;
+    h->col_min[c] = gmin;
+    h->col_max[c] = gmax;
   }
-  h.in_use = true;
-  ctx->handles.push_back(h);
+  ctx->handles.push_back(std::move(h));
   return (int)ctx->handles.size() - 1;
 }
 
-extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
+extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
+  if (!ctx || !bs) return OBX_INVALID_ARGUMENT;
+  auto h = std::make_unique<obx_handle>();
+  std::vector<dev_block> blocks;
+  int rc = obx_pax_host_load(bs, *h, blocks);
+  if (rc != OBX_SUCCESS) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  obx_handle &h = ctx->handles[handle];
-  if (!h.in_use) return OBX_INVALID_ARGUMENT;
-  (void)hipFree(h.d_buf); (void)hipFree(h.d_blocks); (void)hipFree(h.d_bleaves);
-  (void)hipFree(h.d_pleaves); (void)hipFree(h.d_gtable); (void)hipFree(h.d_gtable_big); (void)hipFree(h.d_proj_scratch);
-  (void)hipFree(h.d_bitmap); (void)hipFree(h.d_row_ids); (void)hipFree(h.d_blk_counts);
-  (void)hipFree(h.d_row_slot); (void)hipFree(h.d_minmax);
-  for (auto *&p : h.d_decode_out) { (void)hipFree(p); p = nullptr; }
-  h = obx_handle();
+  HIP_TRY(hipMalloc(&h->d_buf, h->total_bytes + 64));
+  HIP_TRY(hipMemset(h->d_buf + h->total_bytes, 0, 64));
+  HIP_TRY(hipMemcpy(h->d_buf, bs->data, h->total_bytes, hipMemcpyHostToDevice));
+  return obx_finish_load(ctx, std::move(h), blocks);
+}
+
+extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
+  if (!lookup(ctx, handle)) return OBX_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(ctx->device));
+  ctx->handles[handle].reset();
   return OBX_SUCCESS;
 }
 
@@ -933,6 +760,8 @@ static int prep_query(obx_gpu_ctx *ctx, obx_handle &h,
     uint64_t needed = (uint64_t)h.n_blocks * nl;
     if (h.bleaves_cap < needed) {
       (void)hipFree(h.d_bleaves);
+      h.d_bleaves = nullptr; /* a failed hipMalloc must leave no stale pair */
+      h.bleaves_cap = 0;
       HIP_TRY(hipMalloc(&h.d_bleaves, needed * sizeof(blk_leaf)));
       h.bleaves_cap = needed;
     }
@@ -949,14 +778,41 @@ static int prep_query(obx_gpu_ctx *ctx, obx_handle &h,
 
 #include "obx_jit.inc"
 
+/* the plan-generic filter kernel: LDS-staged when every block fits the
+   stage, the _prog build when the plan carries a combine program */
+static decltype(&k_filter) generic_filter_kernel(const obx_handle &h,
+                                                 const dev_plan_hdr &ph) {
+  return h.lds_ok ? (ph.n_prog ? k_filter_prog_lds : k_filter_lds)
+                  : (ph.n_prog ? k_filter_prog : k_filter);
+}
+
+/* close a verb's timed region: ev_stop, the optional copy of a result into
+   the pinned buffer (queued before the sync, so one wait serves both), the
+   sync, and the device times of the kernel and, after prep_query, the prep */
+static int end_timed(obx_gpu_ctx *ctx, bool prep, const void *result = nullptr,
+                     size_t result_bytes = 0) {
+  HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+  if (result)
+    HIP_TRY(hipMemcpyAsync(ctx->h_result, result, result_bytes,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+  ctx->last_ms = ms; /* per-operator monitoring */
+  if (prep) {
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_p0, ctx->ev_p1));
+    ctx->last_prep_ms = ms;
+  }
+  return OBX_SUCCESS;
+}
 
 extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
                               const obx_filter_desc *filter,
                               int want_row_ids) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   HIP_TRY(hipSetDevice(ctx->device));
-  obx_handle &h = ctx->handles[handle];
   dev_plan_hdr ph;
   dev_leaf plv[OBX_DEV_MAX_LEAVES];
   int rc = prep_query(ctx, h, filter, nullptr, ph, plv);
@@ -1003,22 +859,16 @@ extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
                               nullptr) != hipSuccess)
       return OBX_INTERNAL_ERROR;
   } else {
-    auto kfn = h.lds_ok ? (ph.n_prog ? k_filter_prog_lds : k_filter_lds)
-                        : (ph.n_prog ? k_filter_prog : k_filter);
-    hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+    hipLaunchKernelGGL(generic_filter_kernel(h, ph),
+                       dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
                        ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
                        h.d_pleaves, h.d_bleaves, ph,
                        (h.lds_ok && no_bitmap) ? nullptr : h.d_bitmap,
                        want_row_ids ? h.d_row_ids : nullptr,
                        want_row_ids ? h.d_blk_counts : nullptr, h.d_counters);
   }
-  HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-  ctx->last_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_p0, ctx->ev_p1));
-  ctx->last_prep_ms = ms;
+  rc = end_timed(ctx, true);
+  if (rc != OBX_SUCCESS) return rc;
   unsigned long long cnt[16];
   HIP_TRY(hipMemcpy(cnt, h.d_counters, 16 * 8, hipMemcpyDeviceToHost));
   /* slot 0: legacy kernels; slots 8..15: JIT filter's striped WG sums */
@@ -1029,9 +879,9 @@ extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_fetch_bitmap(obx_gpu_ctx *ctx, int handle, uint8_t *out,
                                     int64_t cap) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
-  obx_handle &h = ctx->handles[handle];
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   if (!h.d_bitmap) return OBX_INVALID_ARGUMENT;
   int64_t bytes = (int64_t)((h.total_rows + 7) / 8);
   if (cap < bytes) return OBX_BUF_NOT_ENOUGH;
@@ -1042,9 +892,9 @@ extern "C" int obx_gpu_fetch_bitmap(obx_gpu_ctx *ctx, int handle, uint8_t *out,
 extern "C" int obx_gpu_fetch_row_ids(obx_gpu_ctx *ctx, int handle,
                                      int32_t *out, int64_t cap,
                                      uint64_t *n_out) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
-  obx_handle &h = ctx->handles[handle];
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   if (!h.d_row_ids) return OBX_INVALID_ARGUMENT;
   if (n_out) *n_out = h.last_survivors;
   if (out) {
@@ -1057,9 +907,9 @@ extern "C" int obx_gpu_fetch_row_ids(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_fetch_blk_counts(obx_gpu_ctx *ctx, int handle,
                                         uint32_t *out, int64_t cap) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
-  obx_handle &h = ctx->handles[handle];
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   if (!h.d_blk_counts) return OBX_INVALID_ARGUMENT;
   if (cap < (int64_t)h.n_blocks) return OBX_BUF_NOT_ENOUGH;
   HIP_TRY(hipMemcpy(out, h.d_blk_counts, h.n_blocks * 4,
@@ -1069,10 +919,10 @@ extern "C" int obx_gpu_fetch_blk_counts(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_decode(obx_gpu_ctx *ctx, int handle,
                               const uint16_t *proj_cols, uint16_t n_proj) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   HIP_TRY(hipSetDevice(ctx->device));
-  obx_handle &h = ctx->handles[handle];
   HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
   if (h.lds_ok && n_proj > 1 && n_proj <= OBX_DEV_MAX_COLS) {
     /* one block stage serves every projected column */
@@ -1108,31 +958,26 @@ extern "C" int obx_gpu_decode(obx_gpu_ctx *ctx, int handle,
                        lnp, (uint32_t)n_proj, (uint8_t *const *)outp,
                        (uint8_t *const *)nullptr);
   } else {
-  for (uint16_t i = 0; i < n_proj; i++) {
-    uint16_t c = proj_cols[i];
-    if (c >= h.n_cols) return OBX_INVALID_ARGUMENT;
-    if (!h.d_decode_out[c])
-      HIP_TRY(hipMalloc(&h.d_decode_out[c], h.total_rows * h.cols[c].len));
-    auto kfn = h.lds_ok ? k_decode_lds : k_decode;
-    hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
-                       ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
-                       (uint32_t)c, (uint32_t)h.cols[c].len,
-                       h.d_decode_out[c], (uint8_t *)nullptr);
+    for (uint16_t i = 0; i < n_proj; i++) {
+      uint16_t c = proj_cols[i];
+      if (c >= h.n_cols) return OBX_INVALID_ARGUMENT;
+      if (!h.d_decode_out[c])
+        HIP_TRY(hipMalloc(&h.d_decode_out[c], h.total_rows * h.cols[c].len));
+      auto kfn = h.lds_ok ? k_decode_lds : k_decode;
+      hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+                         ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
+                         (uint32_t)c, (uint32_t)h.cols[c].len,
+                         h.d_decode_out[c], (uint8_t *)nullptr);
+    }
   }
-  }
-  HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-  ctx->last_ms = ms; /* per-operator monitoring, as the scan verbs */
-  return OBX_SUCCESS;
+  return end_timed(ctx, false);
 }
 
 extern "C" int obx_gpu_fetch_col(obx_gpu_ctx *ctx, int handle, uint16_t col,
                                  uint8_t *out, int64_t cap) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size())
-    return OBX_INVALID_ARGUMENT;
-  obx_handle &h = ctx->handles[handle];
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   if (col >= h.n_cols || !h.d_decode_out[col]) return OBX_INVALID_ARGUMENT;
   int64_t bytes = (int64_t)h.total_rows * h.cols[col].len;
   if (cap < bytes) return OBX_BUF_NOT_ENOUGH;
@@ -1144,10 +989,10 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                                        const obx_filter_desc *filter,
                                        const obx_agg_desc *agg,
                                        obx_agg_result *out) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size() || !out)
-    return OBX_INVALID_ARGUMENT;
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp || !out) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   HIP_TRY(hipSetDevice(ctx->device));
-  obx_handle &h = ctx->handles[handle];
   h.last_rows.clear(); /* no stale pagination after a failed scan */
   dev_plan_hdr ph;
   dev_leaf plv[OBX_DEV_MAX_LEAVES];
@@ -1178,15 +1023,11 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     if (!h.d_row_slot) HIP_TRY(hipMalloc(&h.d_row_slot, h.total_rows + 1));
 
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-    {
-      auto kfn = h.lds_ok ? (ph.n_prog ? k_filter_prog_lds : k_filter_lds)
-                          : (ph.n_prog ? k_filter_prog : k_filter);
-      hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
-                         ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
-                         h.d_pleaves, h.d_bleaves, ph, h.d_bitmap,
-                         (int32_t *)nullptr, (uint32_t *)nullptr,
-                         h.d_counters);
-    }
+    hipLaunchKernelGGL(generic_filter_kernel(h, ph),
+                       dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+                       ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
+                       h.d_pleaves, h.d_bleaves, ph, h.d_bitmap,
+                       (int32_t *)nullptr, (uint32_t *)nullptr, h.d_counters);
     hipLaunchKernelGGL(k_group_pass, dim3(grid_for(h.n_blocks)),
                        dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf, h.d_blocks,
                        h.n_blocks, ph, h.d_bitmap, h.d_row_slot, h.d_gtable,
@@ -1223,18 +1064,9 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                          h.d_counters);
     }
   }
-  HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-  /* table + counters are one allocation: one copy into the pinned buffer,
-     queued before the sync */
-  HIP_TRY(hipMemcpyAsync(ctx->h_result, h.d_gtable,
-                         OBX_RESULT_BYTES(OBX_GTABLE_SLOTS),
-                         hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-  ctx->last_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_p0, ctx->ev_p1));
-  ctx->last_prep_ms = ms;
+  /* table + counters are one allocation: one copy into the pinned buffer */
+  rc = end_timed(ctx, true, h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
+  if (rc != OBX_SUCCESS) return rc;
 
   const gslot *gt = (const gslot *)ctx->h_result;
   size_t n_gt = OBX_GTABLE_SLOTS;
@@ -1331,123 +1163,6 @@ extern "C" uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {
   return host_crc32c(buf, len);
 }
 
-/* ---- CS load glue (obx_cs_load.cpp drives; these own the handle) ------- */
-int obx_cs_alloc_handle(obx_gpu_ctx *ctx, obx_handle **h_out) {
-  if (!ctx) return OBX_INVALID_ARGUMENT;
-  HIP_TRY(hipSetDevice(ctx->device));
-  *h_out = new obx_handle();
-  return OBX_SUCCESS;
-}
-
-int obx_cs_finish_load(obx_gpu_ctx *ctx, obx_handle *h,
-                       const obx_col_schema *cols, uint16_t n_cols,
-                       std::vector<dev_block> &blocks, uint8_t *d_buf,
-                       uint64_t arena_bytes, uint64_t total_rows) {
-  h->d_buf = d_buf;
-  h->n_blocks = (uint32_t)blocks.size();
-  h->n_cols = n_cols;
-  h->total_rows = total_rows;
-  h->total_bytes = arena_bytes;
-  memcpy(h->cols, cols, sizeof(obx_col_schema) * n_cols);
-  bool lds_ok = true;
-  for (uint32_t b = 0; b < h->n_blocks; b++) {
-    const dev_block &db = blocks[b];
-    if ((db.block_byte & 15) || db.block_len + 24 > OBX_LDS_STAGE_BYTES ||
-        db.row_count > 4096)
-      lds_ok = false;
-    for (uint16_t c = 0; c < n_cols; c++) {
-      const dev_col &dc = db.cols[c];
-      uint8_t cls;
-      switch (dc.enc) {
-        case OBX_D_RAW: cls = 0; break;
-        case OBX_D_DICT: cls = 1; break;
-        case OBX_D_INTDIFF: cls = 2; break;
-        case OBX_D_CONST: cls = dc.runs == 0 ? 3 : 4; break;
-        default: cls = 4; break;
-      }
-      if (dc.flags & OBX_DF_STRING) cls |= 0x10;
-      h->col_class.push_back(cls);
-      h->col_cnt.push_back((uint8_t)(dc.count > 254 ? 255 : dc.count));
-      if (b == 0) {
-        h->col_dict_every[c] = true;
-        h->col_dict_any[c] = true;
-        h->col_raw8_every[c] = true;
-        h->col_rangefam_every[c] = true;
-        h->col_maxcnt[c] = 0;
-      }
-      if ((cls & 0xF) != 1 || (cls & 0x10) || dc.count > 63)
-        h->col_dict_every[c] = false;
-      if ((cls & 0xF) != 1 || dc.count > 63) h->col_dict_any[c] = false;
-      if (!(dc.enc == OBX_D_RAW && !(dc.flags & OBX_DF_BITPACK) &&
-            !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT) &&
-            dc.width == 8 && (dc.data_bit & 63) == 0))
-        h->col_raw8_every[c] = false;
-      if (!((dc.enc == OBX_D_RAW || dc.enc == OBX_D_INTDIFF) &&
-            !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT)))
-        h->col_rangefam_every[c] = false;
-      {
-        uint32_t w = 255;
-        if (dc.enc == OBX_D_RAW || dc.enc == OBX_D_DICT ||
-            dc.enc == OBX_D_INTDIFF)
-          w = (dc.flags & OBX_DF_BITPACK) ? dc.width
-                                          : (uint32_t)dc.width * 8;
-        if (w > h->col_maxw[c]) h->col_maxw[c] = w;
-      }
-      if (dc.flags & OBX_DF_HAS_EXT) h->col_ext_any[c] = true;
-    }
-    if (db.row_count > h->max_block_rows) h->max_block_rows = db.row_count;
-    if (db.block_len > h->max_block_len) h->max_block_len = db.block_len;
-  }
-  h->lds_ok = lds_ok;
-  h->n_cus = ctx->n_cus;
-  summarize_col_classes(*h);
-  /* dict payloads live only on the device for CS handles; the persistent
-     JIT path requires the host-verified byte-identical dicts, so it is
-     simply not taken (col_dict_stable stays false -> v1 JIT / generic
-     kernels, which are parity-equal) */
-  HIP_TRY(hipMalloc(&h->d_blocks, sizeof(dev_block) * blocks.size()));
-  HIP_TRY(hipMemcpy(h->d_blocks, blocks.data(),
-                    sizeof(dev_block) * blocks.size(),
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS)));
-  h->d_counters = (unsigned long long *)(h->d_gtable + OBX_GTABLE_SLOTS);
-  HIP_TRY(hipMalloc(&h->d_pleaves, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES));
-  {
-    uint64_t nmm = (uint64_t)h->n_blocks * n_cols * 2;
-    HIP_TRY(hipMalloc(&h->d_minmax, nmm * sizeof(int64_t)));
-    hipLaunchKernelGGL(k_col_minmax, dim3(grid_for(h->n_blocks)),
-                       dim3(OBX_WG_HOST), 0, nullptr, h->d_buf, h->d_blocks,
-                       h->n_blocks, (uint32_t)n_cols, h->d_minmax);
-    std::vector<int64_t> mm(nmm);
-    HIP_TRY(hipMemcpy(mm.data(), h->d_minmax, nmm * sizeof(int64_t),
-                      hipMemcpyDeviceToHost));
-    for (uint16_t c = 0; c < n_cols; c++) {
-      int64_t gmin = INT64_MAX, gmax = INT64_MIN;
-      bool known = true;
-      for (uint32_t b = 0; b < h->n_blocks; b++) {
-        int64_t mn = mm[2 * ((uint64_t)b * n_cols + c)];
-        int64_t mx = mm[2 * ((uint64_t)b * n_cols + c) + 1];
-        if (mn == INT64_MIN && mx == INT64_MAX) { known = false; break; }
-        if (mn <= mx) {
-          if (mn < gmin) gmin = mn;
-          if (mx > gmax) gmax = mx;
-        }
-      }
-      h->col_known[c] = known;
-      h->col_min[c] = gmin;
-      h->col_max[c] = gmax;
-    }
-  }
-  return OBX_SUCCESS;
-}
-
-int obx_cs_publish_handle(obx_gpu_ctx *ctx, obx_handle *h) {
-  h->in_use = true;
-  ctx->handles.push_back(*h);
-  delete h;
-  return (int)ctx->handles.size() - 1;
-}
-
 /* Debug/test-only: generate the hipRTC source the JIT would compile for a
  * plan against synthetic load-time column summaries, without a GPU (the
  * container has no device; tests hipcc-compile the dump offline).
@@ -1470,7 +1185,6 @@ extern "C" int64_t obx_jit_dump_src_ex(
   h.n_cols = n_cols;
   h.n_blocks = n_blocks ? n_blocks : 1;
   if (n_cus) h.n_cus = n_cus;
-  h.lds_ok = true;
   h.max_block_rows = max_block_rows ? max_block_rows : 4096;
   h.max_block_len = OBX_LDS_STAGE_BYTES - 32;
   memcpy(h.cols, cols, sizeof(obx_col_schema) * n_cols);
@@ -1556,17 +1270,53 @@ extern "C" int obx_jit_probe_blocks(
   obx_handle h;
   h.n_cols = n_cols;
   h.n_blocks = n_blocks;
-  h.lds_ok = true;
   memcpy(h.cols, cols, sizeof(obx_col_schema) * n_cols);
-  h.col_class.assign(col_class, col_class + (size_t)n_blocks * n_cols);
-  h.col_cnt.assign(col_cnt, col_cnt + (size_t)n_blocks * n_cols);
-  summarize_col_classes(h);
+  for (size_t b = 0; b < n_blocks; b++) {
+    h.col_class.insert(h.col_class.end(), col_class + b * n_cols,
+                       col_class + (b + 1) * n_cols);
+    h.col_cnt.insert(h.col_cnt.end(), col_cnt + b * n_cols,
+                     col_cnt + (b + 1) * n_cols);
+    summarize_col_classes(h);
+  }
   dev_plan_hdr ph;
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
   int rc = build_plan(h, filter, agg, ph, pl);
   if (rc != OBX_SUCCESS) return rc;
   jit_shape js;
   return jit_plan_shape(ph, js) && jit_blocks_ok(h, ph, js) ? 1 : 0;
+}
+
+/* Debug/test-only: the load-time facts of a blockset, without a GPU. Runs
+ * only the host half of the PAX (is_cs == 0) or CS loader, then writes
+ * handle_out[7] = n_blocks, n_cols, total_rows, total_bytes, lds_ok,
+ * max_block_rows, max_block_len, and per column four words into col_out:
+ * a flag word (1 dict_every, 2 dict_any, 4 dict_stable, 8 grp16_every,
+ * 16 raw8_every, 32 rangefam_every, 64 ext_any, 128 slow_any, 256 span_any),
+ * col_maxcnt, col_maxw, col_cnt_max. Returns the loader's status. */
+extern "C" int obx_probe_load_facts(const obx_blockset *bs, int is_cs,
+                                    uint64_t *handle_out, uint32_t *col_out) {
+  if (!bs || !handle_out || !col_out) return OBX_INVALID_ARGUMENT;
+  obx_handle h;
+  std::vector<dev_block> blocks;
+  int rc = is_cs ? obx_cs_host_load(bs, h, blocks, nullptr)
+                 : obx_pax_host_load(bs, h, blocks);
+  if (rc != OBX_SUCCESS) return rc;
+  const uint64_t hf[7] = {h.n_blocks, h.n_cols, h.total_rows, h.total_bytes,
+                          h.lds_ok, h.max_block_rows, h.max_block_len};
+  memcpy(handle_out, hf, sizeof(hf));
+  for (uint16_t c = 0; c < h.n_cols; c++) {
+    const bool f[9] = {h.col_dict_every[c], h.col_dict_any[c],
+                       h.col_dict_stable[c], h.col_grp16_every[c],
+                       h.col_raw8_every[c], h.col_rangefam_every[c],
+                       h.col_ext_any[c], h.col_slow_any[c], h.col_span_any[c]};
+    uint32_t *o = col_out + 4 * c;
+    o[0] = 0;
+    for (int i = 0; i < 9; i++) o[0] |= (uint32_t)f[i] << i;
+    o[1] = h.col_maxcnt[c];
+    o[2] = h.col_maxw[c];
+    o[3] = h.col_cnt_max[c];
+  }
+  return OBX_SUCCESS;
 }
 
 extern "C" double obx_gpu_last_kernel_ms(obx_gpu_ctx *ctx) {
@@ -1590,16 +1340,16 @@ extern "C" uint32_t obx_gpu_last_grid(obx_gpu_ctx *ctx) {
 }
 
 extern "C" uint64_t obx_gpu_total_rows(obx_gpu_ctx *ctx, int handle) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size()) return 0;
-  return ctx->handles[handle].total_rows;
+  const obx_handle *h = lookup(ctx, handle);
+  return h ? h->total_rows : 0;
 }
 extern "C" uint64_t obx_gpu_total_bytes(obx_gpu_ctx *ctx, int handle) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size()) return 0;
-  return ctx->handles[handle].total_bytes;
+  const obx_handle *h = lookup(ctx, handle);
+  return h ? h->total_bytes : 0;
 }
 extern "C" uint64_t obx_gpu_last_survivors(obx_gpu_ctx *ctx, int handle) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size()) return 0;
-  return ctx->handles[handle].last_survivors;
+  const obx_handle *h = lookup(ctx, handle);
+  return h ? h->last_survivors : 0;
 }
 
 /* paged access to the last scan's full (sorted) group rows — the result
@@ -1610,9 +1360,9 @@ extern "C" int obx_gpu_agg_fetch(obx_gpu_ctx *ctx, int handle,
                                  uint32_t start, uint32_t count,
                                  obx_group_row *out, uint32_t *n_out,
                                  uint64_t *n_total) {
-  if (!ctx || handle < 0 || handle >= (int)ctx->handles.size() || !out)
-    return OBX_INVALID_ARGUMENT;
-  obx_handle &h = ctx->handles[handle];
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp || !out) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
   uint64_t total = h.last_rows.size();
   if (n_total) *n_total = total;
   uint32_t n = 0;

@@ -1,0 +1,232 @@
+/*
+ * obx_host.h — what the two host translation units share (obx_engine.cpp,
+ * obx_cs_load.cpp): the kernel entry points, the loaded-table handle and its
+ * context, and the load steps both loaders run. Private to csrc/; the public
+ * C-ABI is include/obx.h.
+ */
+#ifndef OBX_HOST_H_
+#define OBX_HOST_H_
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <map>
+#include <memory>
+#include <vector>
+
+#include "obx_dev.h"
+
+#define OBX_WG_HOST 256 /* must match the kernels' WG */
+
+#include "../../include/obx.h"
+#include "../../oracle/obx_format.h"
+
+/* kernels (obx_kernels.hip) */
+extern "C" __global__ void k_decode_lds(
+    const uint8_t *, const dev_block *, uint32_t, uint32_t, uint32_t,
+    uint8_t *, uint8_t *);
+extern "C" __global__ void k_decode_multi(
+    const uint8_t *, const dev_block *, uint32_t, const uint16_t *,
+    const uint8_t *, uint32_t, uint8_t *const *, uint8_t *const *);
+extern "C" __global__ void k_scan_agg_direct(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
+extern "C" __global__ void k_scan_filter_agg(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
+extern "C" __global__ void k_scan_filter_agg_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
+extern "C" __global__ void k_filter(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
+    unsigned long long *);
+extern "C" __global__ void k_filter_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
+    unsigned long long *);
+/* _prog variants: compiled with the postfix AND/OR combine-program path
+   (reference: ObPushdownFilterExecutor AND/OR trees); separate entry points
+   so the AND-only fast path keeps its lean register budget. */
+extern "C" __global__ void k_scan_filter_agg_prog(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
+extern "C" __global__ void k_scan_filter_agg_prog_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, gslot *, unsigned long long *);
+extern "C" __global__ void k_filter_prog(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
+    unsigned long long *);
+extern "C" __global__ void k_filter_prog_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, uint64_t *, int32_t *, uint32_t *,
+    unsigned long long *);
+extern "C" __global__ void k_decode(
+    const uint8_t *, const dev_block *, uint32_t, uint32_t, uint32_t,
+    uint8_t *, uint8_t *);
+extern "C" __global__ void k_group_pass(
+    const uint8_t *, const dev_block *, uint32_t, const dev_plan_hdr,
+    const uint64_t *, uint8_t *, gslot *, unsigned long long *);
+extern "C" __global__ void k_agg_pass(
+    const uint8_t *, const dev_block *, uint32_t, const dev_plan_hdr,
+    uint32_t, const uint64_t *, const uint8_t *, gslot *);
+extern "C" __global__ void k_lower_leaves(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *, uint32_t,
+    uint32_t, const int64_t *, blk_leaf *);
+extern "C" __global__ void k_col_minmax(
+    const uint8_t *, const dev_block *, uint32_t, uint32_t, int64_t *);
+extern "C" __global__ void k_gtable_init(
+    unsigned long long *, uint32_t, uint32_t, uint32_t, uint32_t);
+
+#define HIP_TRY(x)                                        \
+  do {                                                    \
+    hipError_t _e = (x);                                  \
+    if (_e != hipSuccess) {                               \
+      fprintf(stderr, "obx: HIP error %s at %s:%d\n",     \
+              hipGetErrorString(_e), __FILE__, __LINE__); \
+      return OBX_INTERNAL_ERROR;                          \
+    }                                                     \
+  } while (0)
+
+/* device memory that lives no longer than its scope (loader staging) */
+template <class T>
+struct dev_tmp {
+  T *p = nullptr;
+  dev_tmp() = default;
+  dev_tmp(const dev_tmp &) = delete;
+  dev_tmp &operator=(const dev_tmp &) = delete;
+  ~dev_tmp() { if (p) (void)hipFree(p); }
+};
+
+/* One loaded table. Owns every device pointer below: ~obx_handle is the one
+   place they are released, so a handle is never copied and lives behind a
+   unique_ptr from the loader's first allocation to free / close. */
+struct obx_handle {
+  obx_handle() = default;
+  obx_handle(const obx_handle &) = delete;
+  obx_handle &operator=(const obx_handle &) = delete;
+  ~obx_handle();
+
+  uint8_t *d_buf = nullptr;
+  dev_block *d_blocks = nullptr;
+  uint32_t n_blocks = 0;
+  uint16_t n_cols = 0;
+  uint64_t total_rows = 0;
+  uint64_t total_bytes = 0;
+  obx_col_schema cols[OBX_DEV_MAX_COLS];
+  /* query scratch */
+  blk_leaf *d_bleaves = nullptr;
+  uint32_t bleaves_cap = 0; /* in (block,leaf) entries */
+  dev_leaf *d_pleaves = nullptr;
+  gslot *d_gtable = nullptr;
+  unsigned long long *d_counters = nullptr; /* tail of d_gtable */
+  uint64_t *d_bitmap = nullptr;
+  int32_t *d_row_ids = nullptr;
+  uint32_t *d_blk_counts = nullptr;
+  uint8_t *d_row_slot = nullptr;
+  uint8_t *d_decode_out[OBX_DEV_MAX_COLS] = {};
+  uint64_t last_survivors = 0;
+  gslot *d_gtable_big = nullptr; /* high-cardinality direct kernel table */
+  void *d_proj_scratch = nullptr; /* k_decode_multi proj/len/out arrays */
+  std::vector<obx_group_row> last_rows; /* full sorted group rows of the
+                                           last scan (obx_gpu_agg_fetch) */
+  uint32_t n_cus = 256; /* compute units of the owning device */
+
+  /* ---- load-time facts (obx_fold_block, once per block) ---------------
+     everything the per-query plan and JIT eligibility tests ask of the
+     blocks, so a query costs O(columns), not O(blocks) */
+  bool lds_ok = true;    /* all blocks 16-B aligned and <= LDS stage size */
+  uint32_t max_block_rows = 0;
+  uint32_t max_block_len = 0;
+  /* per-(block,col) encoding summary: low nibble = decode class (0 raw,
+     1 dict, 2 intdiff, 3 const, 4 slow, 5 span), bit4 = string; col_cnt =
+     dict count capped at 255. Kept for the exact per-block cell product of
+     a two-column grouping (jit_pair_cells_max, obx_jit.inc) */
+  std::vector<uint8_t> col_class, col_cnt;
+  bool col_span_any[OBX_DEV_MAX_COLS] = {};    /* class 5 in any block */
+  bool col_grp16_every[OBX_DEV_MAX_COLS] = {}; /* class 1 and count < 16 in
+                                                  every block */
+  bool col_slow_any[OBX_DEV_MAX_COLS] = {};    /* class > 3 or string in
+                                                  any block */
+  uint32_t col_cnt_max[OBX_DEV_MAX_COLS] = {}; /* max of col_cnt */
+  /* max over blocks of (cnt[c0]+1)*(cnt[c1]+1), filled on the first query
+     that groups by (c0, c1) and whose product of column maxima exceeds the
+     16-cell limit (key = c0 << 16 | c1) */
+  mutable std::map<uint32_t, uint32_t> pair_cells_max;
+  bool col_dict_every[OBX_DEV_MAX_COLS] = {}; /* class==1, not string, and
+                                                 count<=63 in every block */
+  bool col_dict_any[OBX_DEV_MAX_COLS] = {};   /* dict (incl. char) with
+                                                 count<=63 in every block */
+  bool col_dict_stable[OBX_DEV_MAX_COLS] = {}; /* dict_any AND the dict
+                                                  payload is byte-identical
+                                                  in every block (group/ref
+                                                  persistence; numeric-only
+                                                  uses additionally require
+                                                  col_dict_every). PAX only */
+  bool col_ext_any[OBX_DEV_MAX_COLS] = {};  /* HAS_EXT in any block */
+  bool col_raw8_every[OBX_DEV_MAX_COLS] = {}; /* 8-B RAW, 64-bit-aligned,
+                                                 no ext, in every block */
+  bool col_rangefam_every[OBX_DEV_MAX_COLS] = {}; /* RAW numeric / INTDIFF
+                                                     (packed-range lowerable)
+                                                     in every block */
+  uint32_t col_maxcnt[OBX_DEV_MAX_COLS] = {}; /* max dict count, uncapped */
+  uint32_t col_maxw[OBX_DEV_MAX_COLS] = {};   /* max packed width (bits)
+                                                 across blocks; 255 = no
+                                                 packed stream (slow enc) */
+
+  /* stored skip index: per-(block,col) [min,max] of non-null decoded
+     values, captured by k_col_minmax at load (device copy feeds
+     k_lower_leaves pruning; host summary feeds the JIT's i64-accumulator
+     range eligibility, obx_jit.inc) */
+  int64_t *d_minmax = nullptr;
+  int64_t col_min[OBX_DEV_MAX_COLS] = {};   /* global over blocks */
+  int64_t col_max[OBX_DEV_MAX_COLS] = {};
+  bool col_known[OBX_DEV_MAX_COLS] = {};    /* bounds known in EVERY block */
+};
+
+struct obx_gpu_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+  double last_ms = 0.0;
+  double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
+  int last_jit = 0;           /* last scan used the specialized kernel */
+  uint32_t last_grid = 0;     /* workgroups that kernel was launched with */
+  uint32_t n_cus = 256;
+  /* pinned landing buffer for the group table + counters of a scan (sized
+     for the growth-path table) */
+  uint8_t *h_result = nullptr;
+  /* a handle's id is its index here: never reused, null once freed */
+  std::vector<std::unique_ptr<obx_handle>> handles;
+};
+
+static inline uint32_t grid_for(uint32_t n_blocks) {
+  uint32_t g = n_blocks < 4096u ? n_blocks : 4096u;
+  return g ? g : 1;
+}
+
+/* ---- loading: host half, arena upload, finish (obx_engine.cpp) ----------
+   A loader parses its format into dev_blocks without a HIP call, folding
+   each into the handle's facts; uploads h->d_buf in its own way (PAX: a
+   copy, CS: k_cs_decode); and hands the handle to obx_finish_load. */
+
+/* fold one parsed block into every per-column and per-handle fact */
+void obx_fold_block(obx_handle &h, const dev_block &db);
+
+/* upload the descriptors, allocate the query scratch, capture the min/max
+   skip index, and publish the handle: returns its id, or a negative status
+   (the handle and all it holds are then released) */
+int obx_finish_load(obx_gpu_ctx *ctx, std::unique_ptr<obx_handle> h,
+                    const std::vector<dev_block> &blocks);
+
+/* the loaders' host halves: schema checks + parse + fold, no HIP call */
+int obx_pax_host_load(const obx_blockset *bs, obx_handle &h,
+                      std::vector<dev_block> &blocks);
+struct obx_cs_plan; /* device decode tasks (obx_cs_load.cpp) */
+int obx_cs_host_load(const obx_blockset *bs, obx_handle &h,
+                     std::vector<dev_block> &blocks,
+                     obx_cs_plan *plan /* null: facts only */);
+
+#endif /* OBX_HOST_H_ */
