@@ -353,6 +353,48 @@ int obx_gpu_decode(obx_gpu_ctx *ctx, int handle, const uint16_t *proj_cols,
 int obx_gpu_fetch_col(obx_gpu_ctx *ctx, int handle, uint16_t col,
                       uint8_t *out, int64_t cap);
 
+/* get_rows(row_ids) for a whole scan range (ObIMicroBlockReader::get_rows
+ * with the selection vector of the pushdown filter): run `filter` (NULL or
+ * n_leaves == 0 = every row), then decode ONLY the surviving rows of the
+ * n_proj projected columns into dense device vectors, in table order (block
+ * order, then row order within the block). *n_rows = survivors. proj_cols
+ * may repeat a column; n_proj is 1..8. With a filter the handle's filter
+ * state (bitmap, row ids, block counts, last_survivors) is left as
+ * obx_gpu_filter(..., want_row_ids = 1) leaves it, and obx_gpu_last_jit
+ * reports the filter stage; without one that state is not touched.
+ * obx_gpu_decode's buffers are separate. obx_gpu_last_kernel_ms = filter +
+ * block-offset scan + gather. A failed call leaves no result to fetch. */
+int obx_gpu_scan_project(obx_gpu_ctx *ctx, int handle,
+                         const obx_filter_desc *filter,
+                         const uint16_t *proj_cols, uint16_t n_proj,
+                         int want_row_nos, uint64_t *n_rows);
+
+/* One ObBatchRows-style window [start, start+count) of projected column
+ * proj_idx (position in proj_cols): count' datums of cols[c].len bytes into
+ * out (cap bytes), and, if out_nulls != NULL, count' bits (nulls_cap bytes),
+ * bit i = row start+i of the result, LSB-first, 1 = NULL (the polarity and
+ * bit order of obx_decode_block's null bitmaps). A NULL row's datum bytes
+ * are all zero. count' = *n_out: what is left of the result from `start`,
+ * at most count; 0 (and success) when start is at or past the end. out and
+ * out_nulls may each be NULL to skip that part; with both NULL the call
+ * only reports *n_out. OBX_BUF_NOT_ENOUGH if a buffer is smaller than the
+ * window needs. */
+int obx_gpu_fetch_proj(obx_gpu_ctx *ctx, int handle, uint16_t proj_idx,
+                       uint64_t start, uint64_t count,
+                       uint8_t *out, int64_t cap,
+                       uint8_t *out_nulls, int64_t nulls_cap, uint64_t *n_out);
+
+/* table-global row numbers (block's first row + block-local id) of the same
+ * window (cap in entries); only after a scan_project with
+ * want_row_nos != 0 */
+int obx_gpu_fetch_proj_row_nos(obx_gpu_ctx *ctx, int handle, uint64_t start,
+                               uint64_t count, uint64_t *out, int64_t cap,
+                               uint64_t *n_out);
+
+/* device milliseconds of one stage of the last obx_gpu_scan_project:
+ * 0 = filter, 1 = block-offset scan, 2 = gather-decode */
+double obx_gpu_last_proj_stage_ms(obx_gpu_ctx *ctx, int stage);
+
 /* Fused scan->filter->aggregate (the benchmark path). */
 int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                             const obx_filter_desc *filter,

@@ -20,7 +20,8 @@ PYEOF
 # again inside a query (one ~240 ms step). Device code is not affected.
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
     -Xarch_host -ftrivial-auto-var-init=zero \
-    obx_engine.cpp obx_kernels.hip obx_cs_load.cpp obx_cs_kernels.hip \
+    obx_engine.cpp obx_kernels.hip obx_project.hip obx_cs_load.cpp \
+    obx_cs_kernels.hip \
     -L/opt/rocm/lib -lhiprtc \
     -o ../libobx.so
 echo "built oceanbase_amd/libobx.so"

@@ -34,6 +34,7 @@ extern "C" int obx_gpu_open(int device, obx_gpu_ctx **out) {
   HIP_TRY(hipEventCreate(&ctx->ev_stop));
   HIP_TRY(hipEventCreate(&ctx->ev_p0));
   HIP_TRY(hipEventCreate(&ctx->ev_p1));
+  HIP_TRY(hipEventCreate(&ctx->ev_mid));
   {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -51,7 +52,8 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->handles.clear(); /* ~obx_handle, while the device is current */
   (void)hipStreamDestroy(ctx->stream);
-  for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1})
+  for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1,
+                        ctx->ev_mid})
     (void)hipEventDestroy(ev);
   (void)hipHostFree(ctx->h_result);
   delete ctx;
@@ -64,10 +66,13 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
 obx_handle::~obx_handle() {
   void *owned[] = {d_buf, d_blocks, d_bleaves, d_pleaves, d_gtable,
                    d_gtable_big, d_proj_scratch, d_bitmap, d_row_ids,
-                   d_blk_counts, d_row_slot, d_minmax};
+                   d_blk_counts, d_row_slot, d_minmax, d_sel_nulls,
+                   d_sel_row_nos, d_blk_off, d_tile_sums, d_sel_bits};
   for (void *p : owned)
     if (p) (void)hipFree(p);
   for (uint8_t *p : d_decode_out)
+    if (p) (void)hipFree(p);
+  for (uint8_t *p : d_sel_out)
     if (p) (void)hipFree(p);
 }
 
@@ -806,12 +811,10 @@ static int end_timed(obx_gpu_ctx *ctx, bool prep, const void *result = nullptr,
   return OBX_SUCCESS;
 }
 
-extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
-                              const obx_filter_desc *filter,
-                              int want_row_ids) {
-  obx_handle *hp = lookup(ctx, handle);
-  if (!hp) return OBX_INVALID_ARGUMENT;
-  obx_handle &h = *hp;
+/* the filter verb on a resolved handle: obx_gpu_filter, and the first step
+   of obx_gpu_scan_project (with row ids) */
+static int run_filter(obx_gpu_ctx *ctx, obx_handle &h,
+                      const obx_filter_desc *filter, int want_row_ids) {
   HIP_TRY(hipSetDevice(ctx->device));
   dev_plan_hdr ph;
   dev_leaf plv[OBX_DEV_MAX_LEAVES];
@@ -875,6 +878,14 @@ extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
   h.last_survivors = cnt[0];
   for (int i2 = 8; i2 < 16; i2++) h.last_survivors += cnt[i2];
   return OBX_SUCCESS;
+}
+
+extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
+                              const obx_filter_desc *filter,
+                              int want_row_ids) {
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  return run_filter(ctx, *hp, filter, want_row_ids);
 }
 
 extern "C" int obx_gpu_fetch_bitmap(obx_gpu_ctx *ctx, int handle, uint8_t *out,
@@ -983,6 +994,181 @@ extern "C" int obx_gpu_fetch_col(obx_gpu_ctx *ctx, int handle, uint16_t col,
   if (cap < bytes) return OBX_BUF_NOT_ENOUGH;
   HIP_TRY(hipMemcpy(out, h.d_decode_out[col], bytes, hipMemcpyDeviceToHost));
   return OBX_SUCCESS;
+}
+
+/* grow-only device buffer: reallocates when `need` units exceed `cap`; a
+   failed hipMalloc leaves no stale pair */
+template <class T>
+static int grow(T *&p, uint64_t &cap, uint64_t need, size_t unit) {
+  if (need <= cap) return OBX_SUCCESS;
+  (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc(&p, need * unit));
+  cap = need;
+  return OBX_SUCCESS;
+}
+
+/* get_rows(row_ids) for a whole scan range: filter (with row ids), block
+   offsets, gather-decode of the survivors (obx_project.hip). The only host
+   wait between device steps is the filter's own, whose survivor count sizes
+   the outputs; the offset scan and the gather follow each other on the
+   stream. */
+extern "C" int obx_gpu_scan_project(obx_gpu_ctx *ctx, int handle,
+                                    const obx_filter_desc *filter,
+                                    const uint16_t *proj_cols, uint16_t n_proj,
+                                    int want_row_nos, uint64_t *n_rows) {
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
+  h.sel_n_proj = 0; /* a failed call leaves no result behind */
+  if (!proj_cols || n_proj == 0 || n_proj > OBX_DEV_MAX_COLS)
+    return OBX_INVALID_ARGUMENT;
+  for (uint16_t i = 0; i < n_proj; i++)
+    if (proj_cols[i] >= h.n_cols) return OBX_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(ctx->device));
+
+  const bool filtered = filter && filter->n_leaves;
+  uint64_t total = h.total_rows;
+  ctx->last_proj_ms[0] = ctx->last_proj_ms[1] = ctx->last_proj_ms[2] = 0.0;
+  if (filtered) {
+    int rc = run_filter(ctx, h, filter, 1);
+    if (rc != OBX_SUCCESS) return rc;
+    ctx->last_proj_ms[0] = ctx->last_ms;
+    total = h.last_survivors;
+  } else {
+    ctx->last_jit = 0; /* no filter stage ran */
+  }
+
+  if (total > 0) {
+    proj_args pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.n_proj = n_proj;
+    for (uint16_t i = 0; i < n_proj; i++) {
+      const uint16_t c = proj_cols[i];
+      int rc = grow(h.d_sel_out[i], h.sel_out_cap[i], total * h.cols[c].len, 1);
+      if (rc != OBX_SUCCESS) return rc;
+      pa.out[i] = h.d_sel_out[i];
+      pa.col[i] = c;
+      pa.len[i] = h.cols[c].len;
+    }
+    int rc = grow(h.d_sel_nulls, h.sel_nulls_cap, total, 1);
+    if (rc != OBX_SUCCESS) return rc;
+    if (want_row_nos) {
+      rc = grow(h.d_sel_row_nos, h.sel_row_nos_cap, total, sizeof(uint64_t));
+      if (rc != OBX_SUCCESS) return rc;
+    }
+    const uint32_t n_tiles = (h.n_blocks + OBX_PROJ_TILE - 1) / OBX_PROJ_TILE;
+    if (filtered && !h.d_blk_off) {
+      HIP_TRY(hipMalloc(&h.d_blk_off, ((uint64_t)h.n_blocks + 1) * 8));
+      HIP_TRY(hipMalloc(&h.d_tile_sums, (uint64_t)n_tiles * 8));
+    }
+
+    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    if (filtered) {
+      hipLaunchKernelGGL(k_project_tile_sums, dim3(n_tiles), dim3(OBX_WG_HOST),
+                         0, ctx->stream, h.d_blk_counts, h.n_blocks,
+                         h.d_tile_sums);
+      hipLaunchKernelGGL(k_project_offsets, dim3(n_tiles), dim3(OBX_WG_HOST),
+                         0, ctx->stream, h.d_blk_counts, h.n_blocks,
+                         h.d_tile_sums, h.d_blk_off);
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_mid, ctx->stream));
+    hipLaunchKernelGGL(h.lds_ok ? k_project_sel_lds : k_project_sel,
+                       dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+                       ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
+                       filtered ? h.d_row_ids : (const int32_t *)nullptr,
+                       filtered ? h.d_blk_counts : (const uint32_t *)nullptr,
+                       filtered ? h.d_blk_off : (const uint64_t *)nullptr, pa,
+                       h.d_sel_nulls,
+                       want_row_nos ? h.d_sel_row_nos : (uint64_t *)nullptr,
+                       total);
+    rc = end_timed(ctx, false);
+    if (rc != OBX_SUCCESS) return rc;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_mid));
+    ctx->last_proj_ms[1] = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_mid, ctx->ev_stop));
+    ctx->last_proj_ms[2] = ms;
+  }
+  /* filter + offset scan + gather together */
+  ctx->last_ms = ctx->last_proj_ms[0] + ctx->last_proj_ms[1] +
+                 ctx->last_proj_ms[2];
+
+  memcpy(h.sel_cols, proj_cols, sizeof(uint16_t) * n_proj);
+  h.sel_has_row_nos = want_row_nos != 0;
+  h.sel_rows = total;
+  h.sel_n_proj = n_proj;
+  if (n_rows) *n_rows = total;
+  return OBX_SUCCESS;
+}
+
+/* the rows of [start, start + count) that the result holds */
+static uint64_t sel_window(const obx_handle &h, uint64_t start,
+                           uint64_t count) {
+  if (start >= h.sel_rows) return 0;
+  return count < h.sel_rows - start ? count : h.sel_rows - start;
+}
+
+extern "C" int obx_gpu_fetch_proj(obx_gpu_ctx *ctx, int handle,
+                                  uint16_t proj_idx, uint64_t start,
+                                  uint64_t count, uint8_t *out, int64_t cap,
+                                  uint8_t *out_nulls, int64_t nulls_cap,
+                                  uint64_t *n_out) {
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
+  if (proj_idx >= h.sel_n_proj) return OBX_INVALID_ARGUMENT;
+  const uint64_t n = sel_window(h, start, count);
+  if (n_out) *n_out = n;
+  if (n == 0) return OBX_SUCCESS;
+  const uint64_t len = h.cols[h.sel_cols[proj_idx]].len;
+  const uint64_t null_bytes = (n + 7) / 8;
+  if (out && (cap < 0 || (uint64_t)cap < n * len)) return OBX_BUF_NOT_ENOUGH;
+  if (out_nulls && (nulls_cap < 0 || (uint64_t)nulls_cap < null_bytes))
+    return OBX_BUF_NOT_ENOUGH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (out)
+    HIP_TRY(hipMemcpyAsync(out, h.d_sel_out[proj_idx] + start * len, n * len,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  if (out_nulls) {
+    int rc = grow(h.d_sel_bits, h.sel_bits_cap, null_bytes, 1);
+    if (rc != OBX_SUCCESS) return rc;
+    uint64_t g = (null_bytes + OBX_WG_HOST - 1) / OBX_WG_HOST;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(k_project_pack_nulls, dim3((uint32_t)g),
+                       dim3(OBX_WG_HOST), 0, ctx->stream, h.d_sel_nulls,
+                       start, n, (uint32_t)proj_idx, h.d_sel_bits);
+    HIP_TRY(hipMemcpyAsync(out_nulls, h.d_sel_bits, null_bytes,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return OBX_SUCCESS;
+}
+
+extern "C" int obx_gpu_fetch_proj_row_nos(obx_gpu_ctx *ctx, int handle,
+                                          uint64_t start, uint64_t count,
+                                          uint64_t *out, int64_t cap,
+                                          uint64_t *n_out) {
+  obx_handle *hp = lookup(ctx, handle);
+  if (!hp) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
+  if (!h.sel_n_proj || !h.sel_has_row_nos) return OBX_INVALID_ARGUMENT;
+  const uint64_t n = sel_window(h, start, count);
+  if (n_out) *n_out = n;
+  if (n == 0 || !out) return OBX_SUCCESS;
+  if (cap < 0 || (uint64_t)cap < n) return OBX_BUF_NOT_ENOUGH;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out, h.d_sel_row_nos + start, n * sizeof(uint64_t),
+                         hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return OBX_SUCCESS;
+}
+
+/* device time of one stage of the last scan_project: 0 filter, 1 block
+   offsets, 2 gather-decode (their sum is obx_gpu_last_kernel_ms) */
+extern "C" double obx_gpu_last_proj_stage_ms(obx_gpu_ctx *ctx, int stage) {
+  return ctx && stage >= 0 && stage < 3 ? ctx->last_proj_ms[stage] : -1.0;
 }
 
 extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,

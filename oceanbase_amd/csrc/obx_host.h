@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "obx_dev.h"
+#include "obx_project.h"
 
 #define OBX_WG_HOST 256 /* must match the kernels' WG */
 
@@ -79,6 +80,22 @@ extern "C" __global__ void k_col_minmax(
 extern "C" __global__ void k_gtable_init(
     unsigned long long *, uint32_t, uint32_t, uint32_t, uint32_t);
 
+/* filtered projection (obx_project.hip) */
+extern "C" __global__ void k_project_tile_sums(const uint32_t *, uint32_t,
+                                               uint64_t *);
+extern "C" __global__ void k_project_offsets(const uint32_t *, uint32_t,
+                                             const uint64_t *, uint64_t *);
+extern "C" __global__ void k_project_sel(
+    const uint8_t *, const dev_block *, uint32_t, const int32_t *,
+    const uint32_t *, const uint64_t *, const proj_args, uint8_t *,
+    uint64_t *, uint64_t);
+extern "C" __global__ void k_project_sel_lds(
+    const uint8_t *, const dev_block *, uint32_t, const int32_t *,
+    const uint32_t *, const uint64_t *, const proj_args, uint8_t *,
+    uint64_t *, uint64_t);
+extern "C" __global__ void k_project_pack_nulls(const uint8_t *, uint64_t,
+                                                uint64_t, uint32_t, uint8_t *);
+
 #define HIP_TRY(x)                                        \
   do {                                                    \
     hipError_t _e = (x);                                  \
@@ -129,6 +146,23 @@ struct obx_handle {
   uint64_t last_survivors = 0;
   gslot *d_gtable_big = nullptr; /* high-cardinality direct kernel table */
   void *d_proj_scratch = nullptr; /* k_decode_multi proj/len/out arrays */
+  /* result of the last obx_gpu_scan_project: dense vectors per projected
+     position, one byte of null flags per row (bit p = position p), row
+     numbers if asked. The buffers grow only when a result needs more and
+     are kept across calls; sel_n_proj == 0 = no result to fetch. */
+  uint8_t *d_sel_out[OBX_DEV_MAX_COLS] = {};
+  uint64_t sel_out_cap[OBX_DEV_MAX_COLS] = {}; /* bytes */
+  uint8_t *d_sel_nulls = nullptr;
+  uint64_t *d_sel_row_nos = nullptr;
+  uint64_t sel_nulls_cap = 0, sel_row_nos_cap = 0; /* rows */
+  uint64_t *d_blk_off = nullptr;   /* n_blocks + 1 exclusive block offsets */
+  uint64_t *d_tile_sums = nullptr; /* per-tile sums of that scan */
+  uint8_t *d_sel_bits = nullptr;   /* a fetch window's packed null bits */
+  uint64_t sel_bits_cap = 0;       /* bytes */
+  uint16_t sel_cols[OBX_DEV_MAX_COLS] = {};
+  uint16_t sel_n_proj = 0;
+  bool sel_has_row_nos = false;
+  uint64_t sel_rows = 0;
   std::vector<obx_group_row> last_rows; /* full sorted group rows of the
                                            last scan (obx_gpu_agg_fetch) */
   uint32_t n_cus = 256; /* compute units of the owning device */
@@ -190,9 +224,12 @@ struct obx_gpu_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+  hipEvent_t ev_mid = nullptr; /* scan_project: offsets done, gather next */
   double last_ms = 0.0;
   double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
   int last_jit = 0;           /* last scan used the specialized kernel */
+  /* device times of the last scan_project: filter, block offsets, gather */
+  double last_proj_ms[3] = {0.0, 0.0, 0.0};
   uint32_t last_grid = 0;     /* workgroups that kernel was launched with */
   uint32_t n_cus = 256;
   /* pinned landing buffer for the group table + counters of a scan (sized

@@ -54,6 +54,23 @@ def _load():
     lib.obx_gpu_fetch_col.restype = C.c_int
     lib.obx_gpu_fetch_col.argtypes = [C.c_void_p, C.c_int, C.c_uint16,
                                       C.c_void_p, C.c_int64]
+    lib.obx_gpu_scan_project.restype = C.c_int
+    lib.obx_gpu_scan_project.argtypes = [C.c_void_p, C.c_int,
+                                         C.POINTER(abi.FilterDesc),
+                                         C.POINTER(C.c_uint16), C.c_uint16,
+                                         C.c_int, C.POINTER(C.c_uint64)]
+    lib.obx_gpu_fetch_proj.restype = C.c_int
+    lib.obx_gpu_fetch_proj.argtypes = [C.c_void_p, C.c_int, C.c_uint16,
+                                       C.c_uint64, C.c_uint64, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_int64,
+                                       C.POINTER(C.c_uint64)]
+    lib.obx_gpu_fetch_proj_row_nos.restype = C.c_int
+    lib.obx_gpu_fetch_proj_row_nos.argtypes = [C.c_void_p, C.c_int,
+                                               C.c_uint64, C.c_uint64,
+                                               C.c_void_p, C.c_int64,
+                                               C.POINTER(C.c_uint64)]
+    lib.obx_gpu_last_proj_stage_ms.restype = C.c_double
+    lib.obx_gpu_last_proj_stage_ms.argtypes = [C.c_void_p, C.c_int]
     lib.obx_gpu_scan_filter_agg.restype = C.c_int
     lib.obx_gpu_scan_filter_agg.argtypes = [C.c_void_p, C.c_int,
                                             C.POINTER(abi.FilterDesc),
@@ -179,6 +196,75 @@ class GpuEngine:
         if rc != 0:
             raise RuntimeError(f"fetch_col failed: {rc}")
         return out
+
+    def scan_project(self, handle, filter_desc, cols, want_row_nos=False):
+        """Filter, then decode only the survivors of `cols` (a list of
+        column indices, repeats allowed) into dense device vectors in table
+        order. filter_desc None = every row. Returns the survivor count;
+        fetch_proj / fetch_proj_row_nos page the result out."""
+        arr = (C.c_uint16 * len(cols))(*cols)
+        n = C.c_uint64(0)
+        rc = self._lib.obx_gpu_scan_project(
+            self._ctx, handle,
+            C.byref(filter_desc) if filter_desc is not None else None,
+            arr, len(cols), 1 if want_row_nos else 0, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"obx_gpu_scan_project failed: {rc}")
+        return int(n.value)
+
+    def _proj_window(self, handle, proj_idx, start, count):
+        """rows of [start, start+count) the last scan_project holds"""
+        n = C.c_uint64(0)
+        rc = self._lib.obx_gpu_fetch_proj(
+            self._ctx, handle, proj_idx, start,
+            count if count is not None else 2**63, None, 0, None, 0,
+            C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"obx_gpu_fetch_proj failed: {rc}")
+        return int(n.value)
+
+    def fetch_proj(self, handle, proj_idx, datum_len, start=0, count=None):
+        """Window [start, start+count) (count None = to the end) of
+        projected position proj_idx -> (uint8 array of n*datum_len datum
+        bytes, uint8 array of ceil(n/8) null-bitmap bytes: bit i, LSB-first,
+        is row start+i, 1 = NULL). NULL rows' datum bytes are zero."""
+        import numpy as np
+        n = self._proj_window(handle, proj_idx, start, count)
+        out = np.zeros(n * datum_len, dtype=np.uint8)
+        nulls = np.zeros((n + 7) // 8, dtype=np.uint8)
+        got = C.c_uint64(0)
+        rc = self._lib.obx_gpu_fetch_proj(
+            self._ctx, handle, proj_idx, start, n,
+            out.ctypes.data_as(C.c_void_p), out.nbytes,
+            nulls.ctypes.data_as(C.c_void_p), nulls.nbytes, C.byref(got))
+        if rc != 0:
+            raise RuntimeError(f"obx_gpu_fetch_proj failed: {rc}")
+        assert got.value == n
+        return out, nulls
+
+    def fetch_proj_row_nos(self, handle, start=0, count=None):
+        """Table-global row numbers (uint64) of the same window; needs
+        scan_project(..., want_row_nos=True)."""
+        import numpy as np
+        n = C.c_uint64(0)
+        rc = self._lib.obx_gpu_fetch_proj_row_nos(
+            self._ctx, handle, start, count if count is not None else 2**63,
+            None, 0, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"obx_gpu_fetch_proj_row_nos failed: {rc}")
+        out = np.zeros(n.value, dtype=np.uint64)
+        rc = self._lib.obx_gpu_fetch_proj_row_nos(
+            self._ctx, handle, start, n.value,
+            out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"obx_gpu_fetch_proj_row_nos failed: {rc}")
+        return out
+
+    def last_proj_stage_ms(self):
+        """(filter, block-offset scan, gather) device ms of the last
+        scan_project; their sum is last_kernel_ms()."""
+        return tuple(float(self._lib.obx_gpu_last_proj_stage_ms(self._ctx, s))
+                     for s in range(3))
 
     def scan_filter_agg(self, handle, filter_desc, agg_desc):
         res = abi.AggResult()
