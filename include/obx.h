@@ -405,12 +405,20 @@ int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
  * filter/scan_filter_agg call (HIP events on the context stream). */
 double obx_gpu_last_kernel_ms(obx_gpu_ctx *ctx);
 /* device time of the last query's prep phase (plan upload +
- * k_lower_leaves) — with last_kernel_ms, the per-operator stats the
- * reference surfaces through sql_plan_monitor. */
+ * k_lower_leaves, and the build of a packed block-descriptor array when
+ * the query was the first of its handle with that column list) — with
+ * last_kernel_ms, the per-operator stats the reference surfaces through
+ * sql_plan_monitor. */
 double obx_gpu_last_prep_ms(obx_gpu_ctx *ctx);
 /* 1 if the last scan_filter_agg ran the hipRTC plan-specialized kernel
  * (query codegen), 0 if the precompiled generic kernels ran. */
 int obx_gpu_last_jit(obx_gpu_ctx *ctx);
+/* 1 if that kernel read the handle's packed block descriptors (one
+ * 128-byte record per block), 0 if it read the load-time descriptors. */
+int obx_gpu_last_bdesc(obx_gpu_ctx *ctx);
+/* packed descriptor arrays the handle has built so far (a handle caches up
+ * to four, one per ordered column list); -1 for an unknown handle. */
+int64_t obx_gpu_bdesc_builds(obx_gpu_ctx *ctx, int handle);
 /* workgroups the last scan_filter_agg launched its plan-specialized kernel
  * with (0 when the generic kernels ran). */
 uint32_t obx_gpu_last_grid(obx_gpu_ctx *ctx);

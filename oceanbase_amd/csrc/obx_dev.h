@@ -168,6 +168,72 @@ typedef struct dev_agg {
 
 #define OBX_DEV_MAX_NEED 12
 
+/* Packed per-block descriptor of the persistent scan JIT: everything that
+ * kernel reads per block, for one ordered column list (the plan's need_cols,
+ * then the filter-leaf columns not among them), in one 128-byte line
+ * instead of the five lines its fields occupy in a dev_block. Built once per
+ * (handle, column list) by k_pack_bdesc and cached on the handle.
+ *
+ * A column slot is one u64: bits 0-31 the data stream's bit offset from the
+ * block start (truncated to 32 bits exactly as the kernel's own
+ * (uint32_t)(data_bit - block_byte * 8) was), bits 32-47 the dict/ref count,
+ * bits 48-55 the packed width in bits (PW() of obx_jit_dev.h), bits 56-63
+ * the dev_col flags. A count above 65535 or a width above 255 bits does not
+ * fit: obx_bdesc_pack_col then returns 0 and the column keeps the dev_block
+ * path (obx_handle::col_bdesc_fit). */
+typedef struct __attribute__((aligned(128))) obx_bdesc {
+  uint64_t block_byte;
+  uint32_t block_len;
+  uint32_t row_count;
+  uint64_t slot[OBX_DEV_MAX_NEED];
+  uint64_t pad[2];
+} obx_bdesc;
+
+/* the ordered column list of one descriptor array (its cache key) */
+typedef struct obx_bdesc_cols {
+  uint16_t c[OBX_DEV_MAX_NEED];
+  uint32_t n;
+} obx_bdesc_cols;
+
+#define OBX_BD_OFF(s) ((uint32_t)(s))
+#define OBX_BD_COUNT(s) ((uint32_t)((s) >> 32) & 0xFFFFu)
+#define OBX_BD_WIDTH(s) ((uint32_t)((s) >> 48) & 0xFFu)
+#define OBX_BD_FLAGS(s) ((uint32_t)((s) >> 56))
+
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+__host__ __device__
+#endif
+static inline int obx_bdesc_pack_col(const dev_col *c, uint64_t block_byte,
+                                     uint64_t *slot) {
+  const uint32_t w = (c->flags & OBX_DF_BITPACK) ? (uint32_t)c->width
+                                                 : (uint32_t)c->width * 8u;
+  const uint32_t off = (uint32_t)(c->data_bit - block_byte * 8);
+  const int fits = c->count <= 0xFFFFu && w <= 0xFFu;
+  *slot = (uint64_t)off | ((uint64_t)(c->count & 0xFFFFu) << 32) |
+          ((uint64_t)(w & 0xFFu) << 48) | ((uint64_t)c->flags << 56);
+  return fits;
+}
+
+/* the whole record; returns 0 if any listed column does not fit */
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+__host__ __device__
+#endif
+static inline int obx_bdesc_pack(const dev_block *b, const uint16_t *cols,
+                                 uint32_t n_cols, obx_bdesc *out) {
+  int fits = 1;
+  out->block_byte = b->block_byte;
+  out->block_len = b->block_len;
+  out->row_count = b->row_count;
+  for (uint32_t i = 0; i < OBX_DEV_MAX_NEED; i++) {
+    out->slot[i] = 0;
+    if (i < n_cols)
+      fits &= obx_bdesc_pack_col(&b->cols[cols[i]], b->block_byte,
+                                 &out->slot[i]);
+  }
+  out->pad[0] = out->pad[1] = 0;
+  return fits;
+}
+
 /* aggregate-pass grouping: aggs whose inputs share <=3 distinct columns run
  * in one row pass (engine builds these in prep_query) */
 typedef struct dev_pass_agg {

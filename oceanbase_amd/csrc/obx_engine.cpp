@@ -35,6 +35,8 @@ extern "C" int obx_gpu_open(int device, obx_gpu_ctx **out) {
   HIP_TRY(hipEventCreate(&ctx->ev_p0));
   HIP_TRY(hipEventCreate(&ctx->ev_p1));
   HIP_TRY(hipEventCreate(&ctx->ev_mid));
+  HIP_TRY(hipEventCreate(&ctx->ev_b0));
+  HIP_TRY(hipEventCreate(&ctx->ev_b1));
   {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -53,7 +55,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   ctx->handles.clear(); /* ~obx_handle, while the device is current */
   (void)hipStreamDestroy(ctx->stream);
   for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1,
-                        ctx->ev_mid})
+                        ctx->ev_mid, ctx->ev_b0, ctx->ev_b1})
     (void)hipEventDestroy(ev);
   (void)hipHostFree(ctx->h_result);
   delete ctx;
@@ -74,6 +76,8 @@ obx_handle::~obx_handle() {
     if (p) (void)hipFree(p);
   for (uint8_t *p : d_sel_out)
     if (p) (void)hipFree(p);
+  for (bdesc_set &s : bdesc)
+    if (s.d) (void)hipFree(s.d);
 }
 
 /* every verb resolves its handle id here: null for a null context, an id
@@ -110,11 +114,17 @@ static uint64_t host_crc32c(const uint8_t *buf, int64_t len) {
    r03_q1_flush.md): 1x 3.00 ms, 2x 2.90, 4x 2.80, 8x 2.76, 12x 2.78,
    16x 2.82, 32x 3.70; 1.5x (a half-empty second wave) 3.22. The one
    source of that grid: the strategy proves its i64 accumulator bound for
-   it and the launch uses it. */
+   it and the launch uses it. OBX_JIT_SGRID=n caps it at n workgroups (the
+   scan-side sibling of OBX_JIT_FGRID): small tables then give a workgroup
+   several blocks, which the block loop's tests and A/B runs need. */
 #define OBX_JIT_GRID_WAVES 8
 static uint32_t jit_grid_for(uint32_t n_blocks, uint32_t n_cus, int wpb) {
   uint64_t g = (uint64_t)(n_cus ? n_cus : 1) * (uint32_t)(wpb > 0 ? wpb : 1) *
                OBX_JIT_GRID_WAVES;
+  if (const char *sg = getenv("OBX_JIT_SGRID")) {
+    const long v = atol(sg);
+    if (v >= 1 && (uint64_t)v < g) g = (uint64_t)v;
+  }
   if (g > n_blocks) g = n_blocks;
   return g ? (uint32_t)g : 1;
 }
@@ -193,6 +203,9 @@ void obx_fold_block(obx_handle &h, const dev_block &db) {
     if (dc.enc == OBX_D_RAW || dc.enc == OBX_D_DICT || dc.enc == OBX_D_INTDIFF)
       w = (dc.flags & OBX_DF_BITPACK) ? dc.width : (uint32_t)dc.width * 8;
     if (w > h.col_maxw[c]) h.col_maxw[c] = w;
+    uint64_t slot;
+    if (!obx_bdesc_pack_col(&dc, db.block_byte, &slot))
+      h.col_bdesc_unfit[c] = true;
   }
   summarize_col_classes(h);
   if (db.row_count > h.max_block_rows) h.max_block_rows = db.row_count;
@@ -781,6 +794,43 @@ static int prep_query(obx_gpu_ctx *ctx, obx_handle &h,
   return OBX_SUCCESS;
 }
 
+/* the handle's packed descriptor array for one ordered column list (the
+   persistent scan JIT's per-block metadata, obx_bdesc): served from the
+   handle, or built on the stream by k_pack_bdesc into the slot of the
+   oldest of OBX_BDESC_SETS arrays. The evicted array is freed with hipFree,
+   which waits for the device, so no earlier scan still reads it. *built
+   says whether this call queued the build. nullptr = allocation failed. */
+static const obx_bdesc *bdesc_get(obx_handle &h, const obx_bdesc_cols &cols,
+                                  hipStream_t stream, bool *built) {
+  *built = false;
+  obx_handle::bdesc_set *victim = nullptr; /* a free slot, else the oldest */
+  for (obx_handle::bdesc_set &s : h.bdesc) {
+    if (s.d && s.cols.n == cols.n &&
+        memcmp(s.cols.c, cols.c, cols.n * sizeof(cols.c[0])) == 0)
+      return s.d;
+    if (!victim || (victim->d && (!s.d || s.born < victim->born)))
+      victim = &s;
+  }
+  if (victim->d) {
+    (void)hipFree(victim->d);
+    victim->d = nullptr;
+  }
+  const uint64_t nb = h.n_blocks ? h.n_blocks : 1;
+  if (hipMalloc(&victim->d, nb * sizeof(obx_bdesc)) != hipSuccess) {
+    victim->d = nullptr;
+    return nullptr;
+  }
+  victim->cols = cols;
+  victim->born = ++h.bdesc_builds;
+  const uint64_t words = (uint64_t)h.n_blocks * 16;
+  hipLaunchKernelGGL(k_pack_bdesc,
+                     dim3((uint32_t)((words + OBX_WG_HOST - 1) / OBX_WG_HOST)),
+                     dim3(OBX_WG_HOST), 0, stream, h.d_blocks, h.n_blocks,
+                     cols, victim->d);
+  *built = true;
+  return victim->d;
+}
+
 #include "obx_jit.inc"
 
 /* the plan-generic filter kernel: LDS-staged when every block fits the
@@ -807,6 +857,11 @@ static int end_timed(obx_gpu_ctx *ctx, bool prep, const void *result = nullptr,
   if (prep) {
     HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_p0, ctx->ev_p1));
     ctx->last_prep_ms = ms;
+    if (ctx->bdesc_built) { /* this query built a descriptor array */
+      ctx->bdesc_built = false;
+      HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_b0, ctx->ev_b1));
+      ctx->last_prep_ms += ms;
+    }
   }
   return OBX_SUCCESS;
 }
@@ -1186,6 +1241,8 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
   if (rc != OBX_SUCCESS) return rc;
   ctx->last_jit = 0;
   ctx->last_grid = 0;
+  ctx->last_bdesc = 0;
+  ctx->bdesc_built = false;
 
   /* init global table + counters on the device (min/max cells need
      INT64_MAX/MIN) */
@@ -1235,9 +1292,19 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
        signature, before the timed region; obx_jit.inc) */
     jit_entry *je = jit_prepare(h, ph, plv);
     ctx->last_jit = je ? g_jit_kind : 0; /* 2 = persistent v2, 1 = v1 */
+    const obx_bdesc *bd = nullptr;
+    if (je && je->bdesc) {
+      /* the first query with this column list pays the build: its device
+         time is added to that query's prep time (end_timed) */
+      HIP_TRY(hipEventRecord(ctx->ev_b0, ctx->stream));
+      bd = bdesc_get(h, je->bd_cols, ctx->stream, &ctx->bdesc_built);
+      if (!bd) return OBX_INTERNAL_ERROR;
+      HIP_TRY(hipEventRecord(ctx->ev_b1, ctx->stream));
+    }
+    ctx->last_bdesc = bd != nullptr;
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     if (je) {
-      if (jit_launch(je, h, ctx->stream, &ctx->last_grid) != 0)
+      if (jit_launch(je, h, bd, ctx->stream, &ctx->last_grid) != 0)
         return OBX_INTERNAL_ERROR;
     } else {
       auto kfn = h.lds_ok
@@ -1388,6 +1455,8 @@ extern "C" int64_t obx_jit_dump_src_ex(
     h.col_max[c] = col_max[c];
     h.col_maxcnt[c] = col_maxcnt[c];
     h.col_maxw[c] = col_maxw ? col_maxw[c] : 255;
+    /* a maximum count past an obx_bdesc slot: some block does not fit */
+    h.col_bdesc_unfit[c] = col_maxcnt[c] > 0xFFFFu;
     uint8_t cls = h.col_dict_every[c] ? 1 : 0;
     if (obx_store_class(cols[c].obj_type) == OBX_SC_STRING) cls |= 0x10;
     h.col_class.push_back(cls);
@@ -1477,8 +1546,8 @@ extern "C" int obx_jit_probe_blocks(
  * handle_out[7] = n_blocks, n_cols, total_rows, total_bytes, lds_ok,
  * max_block_rows, max_block_len, and per column four words into col_out:
  * a flag word (1 dict_every, 2 dict_any, 4 dict_stable, 8 grp16_every,
- * 16 raw8_every, 32 rangefam_every, 64 ext_any, 128 slow_any, 256 span_any),
- * col_maxcnt, col_maxw, col_cnt_max. Returns the loader's status. */
+ * 16 raw8_every, 32 rangefam_every, 64 ext_any, 128 slow_any, 256 span_any,
+ * 512 bdesc_unfit), col_maxcnt, col_maxw, col_cnt_max. Returns the loader's status. */
 extern "C" int obx_probe_load_facts(const obx_blockset *bs, int is_cs,
                                     uint64_t *handle_out, uint32_t *col_out) {
   if (!bs || !handle_out || !col_out) return OBX_INVALID_ARGUMENT;
@@ -1491,13 +1560,14 @@ extern "C" int obx_probe_load_facts(const obx_blockset *bs, int is_cs,
                           h.lds_ok, h.max_block_rows, h.max_block_len};
   memcpy(handle_out, hf, sizeof(hf));
   for (uint16_t c = 0; c < h.n_cols; c++) {
-    const bool f[9] = {h.col_dict_every[c], h.col_dict_any[c],
-                       h.col_dict_stable[c], h.col_grp16_every[c],
-                       h.col_raw8_every[c], h.col_rangefam_every[c],
-                       h.col_ext_any[c], h.col_slow_any[c], h.col_span_any[c]};
+    const bool f[10] = {h.col_dict_every[c], h.col_dict_any[c],
+                        h.col_dict_stable[c], h.col_grp16_every[c],
+                        h.col_raw8_every[c], h.col_rangefam_every[c],
+                        h.col_ext_any[c], h.col_slow_any[c], h.col_span_any[c],
+                        h.col_bdesc_unfit[c]};
     uint32_t *o = col_out + 4 * c;
     o[0] = 0;
-    for (int i = 0; i < 9; i++) o[0] |= (uint32_t)f[i] << i;
+    for (int i = 0; i < 10; i++) o[0] |= (uint32_t)f[i] << i;
     o[1] = h.col_maxcnt[c];
     o[2] = h.col_maxw[c];
     o[3] = h.col_cnt_max[c];
@@ -1518,6 +1588,31 @@ extern "C" double obx_gpu_last_prep_ms(obx_gpu_ctx *ctx) {
 
 extern "C" int obx_gpu_last_jit(obx_gpu_ctx *ctx) {
   return ctx ? ctx->last_jit : 0;
+}
+
+/* 1 if the last scan's specialized kernel read the packed block descriptors
+   (obx_bdesc), 0 if it read dev_block */
+extern "C" int obx_gpu_last_bdesc(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->last_bdesc : 0;
+}
+
+/* how many descriptor arrays this handle has built so far (cache misses) */
+extern "C" int64_t obx_gpu_bdesc_builds(obx_gpu_ctx *ctx, int handle) {
+  obx_handle *h = lookup(ctx, handle);
+  return h ? (int64_t)h->bdesc_builds : -1;
+}
+
+/* Debug/test-only: the packed descriptor of one dev_block for an ordered
+ * column list, by the function k_pack_bdesc runs (obx_bdesc_pack_col),
+ * without a GPU. Returns 1 if every listed count and width fits its slot,
+ * 0 if not (the handle then keeps the dev_block path for that column). */
+extern "C" int obx_bdesc_probe(const dev_block *blk, const uint16_t *cols,
+                               uint32_t n_cols, obx_bdesc *out) {
+  if (!blk || !cols || !out || n_cols > OBX_DEV_MAX_NEED)
+    return OBX_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < n_cols; i++)
+    if (cols[i] >= OBX_DEV_MAX_COLS) return OBX_INVALID_ARGUMENT;
+  return obx_bdesc_pack(blk, cols, n_cols, out);
 }
 
 /* launch grid of the last scan's specialized kernel (0 = generic kernels) */

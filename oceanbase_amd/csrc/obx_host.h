@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <map>
 #include <memory>
@@ -79,6 +80,11 @@ extern "C" __global__ void k_col_minmax(
     const uint8_t *, const dev_block *, uint32_t, uint32_t, int64_t *);
 extern "C" __global__ void k_gtable_init(
     unsigned long long *, uint32_t, uint32_t, uint32_t, uint32_t);
+extern "C" __global__ void k_pack_bdesc(const dev_block *, uint32_t,
+                                        const obx_bdesc_cols, obx_bdesc *);
+static_assert(sizeof(obx_bdesc) == 128 && alignof(obx_bdesc) == 128 &&
+                  offsetof(obx_bdesc, slot) == 16,
+              "k_pack_bdesc writes obx_bdesc as 16 u64 words");
 
 /* filtered projection (obx_project.hip) */
 extern "C" __global__ void k_project_tile_sums(const uint32_t *, uint32_t,
@@ -208,6 +214,23 @@ struct obx_handle {
   uint32_t col_maxw[OBX_DEV_MAX_COLS] = {};   /* max packed width (bits)
                                                  across blocks; 255 = no
                                                  packed stream (slow enc) */
+  bool col_bdesc_unfit[OBX_DEV_MAX_COLS] = {}; /* a count or width of some
+                                                  block does not fit an
+                                                  obx_bdesc slot: plans that
+                                                  read the column keep the
+                                                  dev_block path */
+
+  /* packed per-block descriptors of the persistent scan JIT, one array of
+     n_blocks records per ordered column list, built by the first query
+     that needs the list (bdesc_get, obx_engine.cpp). At most
+     OBX_BDESC_SETS arrays; the oldest is evicted. */
+#define OBX_BDESC_SETS 4
+  struct bdesc_set {
+    obx_bdesc_cols cols = {};
+    obx_bdesc *d = nullptr;
+    uint64_t born = 0; /* build order: the smallest is evicted */
+  } bdesc[OBX_BDESC_SETS];
+  uint64_t bdesc_builds = 0;
 
   /* stored skip index: per-(block,col) [min,max] of non-null decoded
      values, captured by k_col_minmax at load (device copy feeds
@@ -225,9 +248,12 @@ struct obx_gpu_ctx {
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
   hipEvent_t ev_mid = nullptr; /* scan_project: offsets done, gather next */
+  hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr; /* around a k_pack_bdesc */
+  bool bdesc_built = false;   /* the running scan queued that build */
   double last_ms = 0.0;
   double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
   int last_jit = 0;           /* last scan used the specialized kernel */
+  int last_bdesc = 0;         /* ... and it read the packed descriptors */
   /* device times of the last scan_project: filter, block offsets, gather */
   double last_proj_ms[3] = {0.0, 0.0, 0.0};
   uint32_t last_grid = 0;     /* workgroups that kernel was launched with */

@@ -39,6 +39,8 @@ struct jit_entry {
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;
   int wpb = 0; /* v2: workgroups per CU the launch grid is sized to */
+  bool bdesc = false;        /* v2: reads the packed block descriptors ... */
+  obx_bdesc_cols bd_cols = {}; /* ... of this ordered column list */
 };
 
 struct jit_shape {
@@ -226,12 +228,17 @@ static jit_entry *jit_prepare(const obx_handle &h, const dev_plan_hdr &ph,
   jit_build_strategy(h, ph, js, pl, st); /* !ok -> v1 generator */
   if (!st.ok && js.has_mm) return nullptr; /* v1 cannot do MIN/MAX */
   g_jit_kind = st.ok ? 2 : 1;
-  return jit_get(
+  jit_entry *je = jit_get(
       jit_plan_sig(ph) + (st.ok ? jit_strategy_sig(st) : "V1|"),
       [&] {
         return st.ok ? jit_gen_source_v2(ph, js, st) : jit_gen_source(ph, js);
       },
       "k_jit_scan", "obx_jit_src.hip", st.ok ? st.wpb : 0);
+  if (je && st.ok) { /* the signature carries both: same for every hit */
+    je->bdesc = st.bdesc != 0;
+    je->bd_cols = st.bd_cols;
+  }
+  return je;
 }
 
 static jit_entry *jit_prepare_filter(const obx_handle &h,
@@ -254,8 +261,8 @@ static jit_entry *jit_prepare_filter(const obx_handle &h,
       "k_jit_filter", "obx_jit_filter_src.hip", 0);
 }
 
-static int jit_launch(jit_entry *je, obx_handle &h, hipStream_t stream,
-                      uint32_t *grid_out) {
+static int jit_launch(jit_entry *je, obx_handle &h, const obx_bdesc *bd,
+                      hipStream_t stream, uint32_t *grid_out) {
   /* v2 keeps its accumulators for the kernel's lifetime and flushes once
      per workgroup: its grid is a multiple of the resident set (the grid
      the strategy proved its i64 bound for); v1 merges per block and keeps
@@ -263,8 +270,10 @@ static int jit_launch(jit_entry *je, obx_handle &h, hipStream_t stream,
   const uint32_t grid = je->wpb ? jit_grid_for(h.n_blocks, h.n_cus, je->wpb)
                                 : grid_for(h.n_blocks);
   *grid_out = grid;
-  void *args[7] = {&h.d_buf,     &h.d_blocks, &h.n_blocks, &h.d_pleaves,
-                   &h.d_bleaves, &h.d_gtable, &h.d_counters};
+  /* the v2 kernel takes the descriptor array last (null when its strategy
+     reads dev_block); v1 has no such parameter and ignores the entry */
+  void *args[8] = {&h.d_buf,     &h.d_blocks, &h.n_blocks,   &h.d_pleaves,
+                   &h.d_bleaves, &h.d_gtable, &h.d_counters, &bd};
   return hipModuleLaunchKernel(je->fn, grid, 1, 1, OBX_WG_HOST, 1, 1, 0,
                                stream, args, nullptr) == hipSuccess
              ? 0

@@ -18,10 +18,10 @@
    by the exec mask (the LDS destination must stay uniform +
    lane-linear for global_load_lds addressing) */
 __device__ __forceinline__ void stage2(
-    const uint8_t *__restrict__ buf, const dev_block &blk,
+    const uint8_t *__restrict__ buf, uint64_t block_byte, uint32_t block_len,
     uint8_t *dst) {
-  const uint32_t n16 = (blk.block_len + 15) >> 4;
-  const uint8_t *src = buf + blk.block_byte;
+  const uint32_t n16 = (block_len + 15) >> 4;
+  const uint8_t *src = buf + block_byte;
   for (uint32_t i = threadIdx.x; i < n16; i += WG) {
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) uint32_t
@@ -30,6 +30,49 @@ __device__ __forceinline__ void stage2(
              *)(dst + (size_t)i * 16),
         16, 0, 0);
   }
+}
+
+__device__ __forceinline__ void stage2(
+    const uint8_t *__restrict__ buf, const dev_block &blk,
+    uint8_t *dst) {
+  stage2(buf, blk.block_byte, blk.block_len, dst);
+}
+
+/* A blk_leaf (32 B) as its four u64 words, for the scan's packed-descriptor
+   path: mi holds mode in bits 0-7 and invert in bits 8-15. Whole-word loads
+   of a wave-uniform address stay scalar; the byte fields read through the
+   struct compile to vector byte loads. */
+struct jit_leafw {
+  uint64_t mask, lo, hi, mi;
+};
+typedef uint64_t __attribute__((may_alias)) jit_u64a;
+__device__ __forceinline__ jit_leafw jit_load_leafw(
+    const blk_leaf *__restrict__ p) {
+  const jit_u64a *w = (const jit_u64a *)p;
+  jit_leafw l;
+  l.mask = w[0];
+  l.lo = w[1];
+  l.hi = w[2];
+  l.mi = w[3];
+  return l;
+}
+__device__ __forceinline__ blk_leaf jit_leaf_of(const jit_leafw &w) {
+  blk_leaf l;
+  l.mask = w.mask;
+  l.lo = w.lo;
+  l.hi = w.hi;
+  l.mode = (uint8_t)w.mi;
+  l.invert = (uint8_t)(w.mi >> 8);
+  return l;
+}
+/* leaf_class (obx_dev_common.h) over a jit_leafw and the leaf column's
+   dev_col flags */
+__device__ __forceinline__ uint8_t jit_leaf_class(const jit_leafw &w,
+                                                  uint32_t col_flags) {
+  const uint8_t mode = (uint8_t)w.mi;
+  if (mode == OBX_LEAF_NONE) return 0;
+  if (mode == OBX_LEAF_ALL && !(col_flags & OBX_DF_HAS_EXT)) return 1;
+  return 2;
 }
 
 /* 32-bit-offset packed read from an 8-B-aligned base */

@@ -10,8 +10,23 @@
  * 32-bit extraction of packed streams with r * width <= 32 (OBX_JIT_M32=0
  * restores the 64-bit reads), one multiply against a combined u32 factor
  * table for a PROD3 term whose operands are proven to fit (OBX_JIT_CTAB=0
- * restores the two-table product). OBX_JIT_R, OBX_JIT_STRIPES, OBX_JIT_WPB
- * and OBX_JIT_JWS=0 override the rest.
+ * restores the two-table product), per-block geometry from the packed
+ * descriptor (obx_bdesc, obx_dev.h; OBX_JIT_BDESC=0 restores the reads of
+ * dev_block). OBX_JIT_R, OBX_JIT_STRIPES, OBX_JIT_WPB and OBX_JIT_JWS=0
+ * override the rest; OBX_JIT_SGRID=n caps the launch grid.
+ *
+ * Per block (profiles/r05_scan_bdesc.md): what the loop reads of a block --
+ * its byte offset, length and row count, and per column the stream offset,
+ * count, packed width and flags -- is one 128-byte record of an array built
+ * once per (handle, ordered column list) by k_pack_bdesc and cached on the
+ * handle (bdesc_get, obx_engine.cpp); the lowered leaf tests are read as
+ * whole words. The loop head is scalar loads of two cache lines, then the
+ * stage DMA, where dev_block cost four dependent round trips over up to
+ * six lines. Only a CTX value column that needs a full col_ctx still reads
+ * its dev_col; blocks[0] serves the one-time table and key builds and the
+ * flush. Loading the record one block ahead, behind the stage DMA, was
+ * measured and is not carried: two records live across the sweep spill
+ * SGPRs, and it ran slower than loading at the top of the iteration.
  *
  * Experiments that measured neutral or worse are no longer carried here:
  * the scan's overlapped two-phase block loop, the per-workgroup start
@@ -136,7 +151,20 @@ struct jit_strategy {
   uint32_t ctab_db = 0, ctab_dc = 0;
   uint32_t lds_bytes = 0;
   int wpb = 7;
+  /* per-block geometry from the packed descriptor (obx_bdesc) instead of
+     dev_block; bd_cols is the descriptor's column list, need_cols then the
+     leaf columns not among them */
+  uint8_t bdesc = 0;
+  obx_bdesc_cols bd_cols = {};
 };
+
+/* slot of a schema column in the strategy's descriptor list (it is there:
+   jit_build_strategy lists every column the block loop reads) */
+static int jit_bd_slot(const jit_strategy &st, uint16_t col) {
+  for (uint32_t i = 0; i < st.bd_cols.n; i++)
+    if (st.bd_cols.c[i] == col) return (int)i;
+  return -1;
+}
 
 /* max |value| of a column from the stored bounds; false if unknown */
 static bool jit_col_maxabs(const obx_handle &h, uint16_t col, uint64_t *out) {
@@ -628,6 +656,28 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         (h.max_block_rows ? h.max_block_rows : 4096);
     if (jit_sat_mul(max_term, maxrows) >= BOUND) return false;
   }
+  /* packed descriptor: off when the column list outgrows the record or a
+     listed column has a count or width that does not fit its slot */
+  {
+    const char *be = getenv("OBX_JIT_BDESC");
+    bool on = !be || be[0] != '0';
+    obx_bdesc_cols bc = {};
+    auto add = [&](uint16_t col) {
+      for (uint32_t i = 0; i < bc.n; i++)
+        if (bc.c[i] == col) return;
+      if (bc.n >= OBX_DEV_MAX_NEED || h.col_bdesc_unfit[col]) {
+        on = false;
+        return;
+      }
+      bc.c[bc.n++] = col;
+    };
+    for (uint32_t i = 0; on && i < ph.n_need; i++) add(ph.need_cols[i]);
+    for (uint32_t i = 0; on && i < ph.n_leaves; i++) add(st.leaf_cols[i]);
+    if (on) {
+      st.bdesc = 1;
+      st.bd_cols = bc;
+    }
+  }
   st.ok = true;
   return true;
 }
@@ -668,6 +718,13 @@ static std::string jit_strategy_sig(const jit_strategy &st) {
   }
   snprintf(b, sizeof b, "C%d:%u:%u|", st.ctab_agg, st.ctab_db, st.ctab_dc);
   k += b;
+  snprintf(b, sizeof b, "B%d", st.bdesc);
+  k += b;
+  for (uint32_t i = 0; i < st.bd_cols.n; i++) {
+    snprintf(b, sizeof b, ":%u", st.bd_cols.c[i]);
+    k += b;
+  }
+  k += "|";
   if (st.jws_on) {
     snprintf(b, sizeof b, "J%d:%d:%d:%u:%u:%u|", st.jws_ja, st.jws_a0,
              st.jws_a1, st.jws_d0, st.jws_d1, st.jws_cells);
@@ -681,12 +738,85 @@ static std::string jit_strategy_sig(const jit_strategy &st) {
   return k;
 }
 
+/* Block-loop head of the persistent scan when the strategy reads the packed
+   descriptor (st.bdesc): verdict, stage and per-block geometry come from a
+   jmeta in registers, never from blocks[blk] -- except a CTX value column
+   that needs a full col_ctx (not raw8), which reads its dev_col as before.
+   The jmeta is loaded at the top of the iteration: scalar loads from two
+   cache lines (leaf tests, record), then the stage DMA, where dev_block
+   cost four dependent round trips over up to six lines. Loading it one
+   block ahead, behind the stage DMA, measured slower and is not carried
+   (profiles/r05_scan_bdesc.md). */
+static void jit_gen_block_head_bdesc(const dev_plan_hdr &ph,
+                                     const jit_shape &js,
+                                     const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
+  const int NL = ph.n_leaves;
+  char b[1024];
+  s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
+       "gridDim.x) {\n"
+       "    jmeta cm;\n"
+       "    jit_load_meta(cm, bdesc, bleaves, blk);\n"
+       "    uint8_t blk_verdict = 1;\n";
+  for (int i = 0; i < NL; i++) {
+    snprintf(b, sizeof b,
+             "    {\n"
+             "      const uint8_t c = jit_leaf_class(\n"
+             "          cm.lf[%d], OBX_BD_FLAGS(cm.s[%d]));\n"
+             "      if (c == 0) blk_verdict = 0;\n"
+             "      else if (c == 2 && blk_verdict) blk_verdict = 2;\n"
+             "    }\n",
+             i, jit_bd_slot(st, st.leaf_cols[i]));
+    s += b;
+  }
+  s += "    if (blk_verdict == 0) continue;\n"
+       "    __syncthreads(); /* drain previous block's LDS reads */\n"
+       "    stage2(buf, cm.byte, cm.len, lds_blk);\n"
+       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+       "    __syncthreads();\n"
+       "    const uint64_t blk_bit = cm.byte * 8;\n"
+       "    blk_view bv;\n"
+       "    bv.base = lds_blk;\n"
+       "    bv.bit_bias = blk_bit;\n"
+       "    bv.rbase_bit = 0;\n"
+       "    const uint32_t rows = cm.rows;\n"
+       "\n";
+  for (int g = 0; g < NG && g < 2; g++) {
+    const int k = jit_bd_slot(st, ph.need_cols[ph.group_idx[g]]);
+    snprintf(b, sizeof b,
+             "    const uint32_t go%d = OBX_BD_OFF(cm.s[%d]);\n"
+             "    const uint32_t gW%d = OBX_BD_WIDTH(cm.s[%d]);\n"
+             "    const uint32_t gn%d = OBX_BD_COUNT(cm.s[%d]);\n",
+             g, k, g, k, g, k);
+    s += b;
+  }
+  if (NG > 1) s += "    const uint32_t dim0 = gn0 + 1;\n";
+  for (int j = 0; j < js.n_vc; j++) {
+    const int k = jit_bd_slot(st, js.vcol[j]);
+    if (st.vmode[j] == JV_REF)
+      snprintf(b, sizeof b,
+               "    const uint32_t xo%d = OBX_BD_OFF(cm.s[%d]);\n"
+               "    const uint32_t xW%d = OBX_BD_WIDTH(cm.s[%d]);\n"
+               "    const uint32_t xn%d = OBX_BD_COUNT(cm.s[%d]);\n",
+               j, k, j, k, j, k);
+    else if (st.vraw8[j])
+      snprintf(b, sizeof b,
+               "    const uint32_t vb%d = OBX_BD_OFF(cm.s[%d]) >> 3;\n", j, k);
+    else
+      snprintf(b, sizeof b,
+               "    const col_ctx c%d =\n"
+               "        make_col_ctx(blocks[blk].cols[%u], blk_bit);\n",
+               j, (unsigned)js.vcol[j]);
+    s += b;
+  }
+}
+
 static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                                      const jit_shape &js,
                                      const jit_strategy &st) {
   const int NG = ph.n_group_cols;
   const int NL = ph.n_leaves;
-  char b[1024];
+  char b[2048];
   std::string s;
   s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
        "#include \"obx_jit_dev.h\"\n\n";
@@ -698,6 +828,36 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
            st.hist_total > 0 ? st.hist_total : 1, (unsigned)st.stripes,
            (unsigned)st.stage_bytes, st.jcells);
   s += b;
+  if (st.bdesc) {
+    snprintf(b, sizeof b,
+             "#define NBS %u\n"
+             "/* what the block loop needs of one block, in registers: the\n"
+             "   packed descriptor's header and column slots, and the\n"
+             "   block's lowered leaf tests. Wave-uniform, whole words:\n"
+             "   scalar loads. */\n"
+             "struct jmeta {\n"
+             "  uint64_t byte;\n"
+             "  uint32_t len, rows;\n"
+             "  uint64_t s[NBS];\n"
+             "  jit_leafw lf[NL ? NL : 1];\n"
+             "};\n"
+             "__device__ __forceinline__ void jit_load_meta(\n"
+             "    jmeta &m, const obx_bdesc *__restrict__ bdesc,\n"
+             "    const blk_leaf *__restrict__ bleaves, uint32_t blk) {\n"
+             "  const obx_bdesc &d = bdesc[blk];\n"
+             "  m.byte = d.block_byte;\n"
+             "  m.len = d.block_len;\n"
+             "  m.rows = d.row_count;\n"
+             "#pragma unroll\n"
+             "  for (uint32_t i = 0; i < NBS; i++) m.s[i] = d.slot[i];\n"
+             "#pragma unroll\n"
+             "  for (uint32_t i = 0; i < NL; i++)\n"
+             "    m.lf[i] = jit_load_leafw(bleaves + (uint64_t)blk * NL + "
+             "i);\n"
+             "}\n\n",
+             st.bd_cols.n);
+    s += b;
+  }
   snprintf(b, sizeof b,
            "/* Persistent-accumulator scan (the whole-kernel generalization\n"
            "   of the storage group-by pushdown, ObVectorStore::do_group_by):\n"
@@ -714,7 +874,8 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
            "plan_leaves,\n"
            "    const blk_leaf *__restrict__ bleaves, gslot *__restrict__ "
            "gtable,\n"
-           "    unsigned long long *__restrict__ counters) {\n",
+           "    unsigned long long *__restrict__ counters,\n"
+           "    const obx_bdesc *__restrict__ bdesc) {\n",
            st.wpb);
   s += b;
   s += "  __shared__ __attribute__((aligned(16))) uint8_t "
@@ -896,6 +1057,9 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "  __syncthreads();\n"
        "\n";
   /* ---- block loop: stage, per-block preamble, row sweep ---- */
+  if (st.bdesc) {
+    jit_gen_block_head_bdesc(ph, js, st, s);
+  } else {
   s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
        "gridDim.x) {\n"
        "    const dev_block &cur = blocks[blk];\n"
@@ -963,15 +1127,25 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
       s += b;
     }
   }
+  } /* !st.bdesc */
   /* filter leaf preambles (always inline in v2) */
   for (int i = 0; i < NL; i++) {
-    snprintf(b, sizeof b,
-             "    const blk_leaf lb%d = bl[%d];\n"
-             "    const uint32_t l%do =\n"
-             "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
-             "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
-             i, i, i, (unsigned)st.leaf_cols[i], i,
-             (unsigned)st.leaf_cols[i]);
+    if (st.bdesc) {
+      const int k = jit_bd_slot(st, st.leaf_cols[i]);
+      snprintf(b, sizeof b,
+               "    const blk_leaf lb%d = jit_leaf_of(cm.lf[%d]);\n"
+               "    const uint32_t l%do = OBX_BD_OFF(cm.s[%d]);\n"
+               "    const uint32_t l%dW = OBX_BD_WIDTH(cm.s[%d]);\n",
+               i, i, i, k, i, k);
+    } else {
+      snprintf(b, sizeof b,
+               "    const blk_leaf lb%d = bl[%d];\n"
+               "    const uint32_t l%do =\n"
+               "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
+               "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
+               i, i, i, (unsigned)st.leaf_cols[i], i,
+               (unsigned)st.leaf_cols[i]);
+    }
     s += b;
     if (st.leaf_kind[i] == 1) {
       snprintf(b, sizeof b,

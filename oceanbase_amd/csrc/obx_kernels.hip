@@ -1097,6 +1097,26 @@ extern "C" __global__ void k_gtable_init(
   words[i] = v;
 }
 
+/* Packed per-block descriptors of the persistent scan JIT (obx_bdesc,
+ * obx_dev.h), built once per (handle, column list): one thread per u64 word
+ * of a record, so the 128-byte records are written coalesced. Words 0-1 are
+ * the block header, 2-13 the column slots (obx_bdesc_pack_col, the function
+ * the host probe checks), 14-15 padding. */
+extern "C" __global__ void k_pack_bdesc(
+    const dev_block *__restrict__ blocks, uint32_t n_blocks,
+    const obx_bdesc_cols cols, obx_bdesc *__restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t blk = (uint32_t)(i >> 4), w = (uint32_t)i & 15;
+  if (blk >= n_blocks) return;
+  const dev_block &b = blocks[blk];
+  uint64_t v = 0;
+  if (w == 0) v = b.block_byte;
+  else if (w == 1) v = (uint64_t)b.block_len | ((uint64_t)b.row_count << 32);
+  else if (w - 2 < cols.n)
+    (void)obx_bdesc_pack_col(&b.cols[cols.c[w - 2]], b.block_byte, &v);
+  ((uint64_t *)out)[i] = v;
+}
+
 /* Per-(block,column) min/max of the NON-NULL decoded values, captured once
  * at load time — the engine's stored skip index (the reference writes
  * ObSkipIndex min/max rows at encode time, storage/blocksstable/index_block;

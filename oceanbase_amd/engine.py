@@ -82,6 +82,10 @@ def _load():
     lib.obx_gpu_last_prep_ms.argtypes = [C.c_void_p]
     lib.obx_gpu_last_jit.restype = C.c_int
     lib.obx_gpu_last_jit.argtypes = [C.c_void_p]
+    lib.obx_gpu_last_bdesc.restype = C.c_int
+    lib.obx_gpu_last_bdesc.argtypes = [C.c_void_p]
+    lib.obx_gpu_bdesc_builds.restype = C.c_int64
+    lib.obx_gpu_bdesc_builds.argtypes = [C.c_void_p, C.c_int]
     for f in ("obx_gpu_total_rows", "obx_gpu_total_bytes",
               "obx_gpu_last_survivors"):
         getattr(lib, f).restype = C.c_uint64
