@@ -114,6 +114,18 @@ enum obx_white_op {
                         columns, evaluate the expression, keep is-true
                         rows). SQL three-valued logic: NULL operands
                         propagate; a NULL or false result drops the row. */
+  OBX_OP_IN_SET = 11, /* member of a device-resident key set
+                        (obx_gpu_keyset_*): `lo` holds the set id. The
+                        pushed-down join filter (ObExprJoinFilter over
+                        ObRFInFilterVecMsg / ObRFRangeFilterVecMsg /
+                        ObRFBloomFilterMsg, sql/engine/px/p2p_datahub) and
+                        the white IN filter's parameter hash set
+                        (ObWhiteFilterParamHashSet, ob_pushdown_filter.h),
+                        in exact form. A row passes iff its value is not
+                        NULL and equals a key; an empty set passes nothing.
+                        On OBX_T_CHAR columns a key is the datum's
+                        zero-extended little-endian bytes and the compare is
+                        plain equality. GPU engine only. */
 };
 
 /* black-filter bytecode (one byte per op):
@@ -443,11 +455,51 @@ int obx_gpu_agg_fetch(obx_gpu_ctx *ctx, int handle, uint32_t start,
 int obx_cpu_agg_fetch(uint32_t start, uint32_t count, obx_group_row *out,
                       uint32_t *n_out, uint64_t *n_total);
 
+/* ---- key sets: a join's build keys, pushed into the scan ----------------
+ * A set lives in device memory, owned by the context; its id is what an
+ * OBX_OP_IN_SET leaf puts in `lo`. Ids are never reused. A filter that names
+ * an unknown or freed id fails with OBX_INVALID_ARGUMENT. A set has to
+ * outlive only the calls that name it. Two exact forms (csrc/obx_keyset.h):
+ * a bitmap over [min, max] when that is no larger than the hash table
+ * (span <= 64 * slots, and never past 2^33 bits), else open addressing over
+ * max(64, pow2ceil(2 n)) slots. */
+typedef struct obx_keyset_info {
+  uint64_t n_keys_in;     /* keys the build read (non-null) */
+  uint64_t n_distinct;    /* distinct keys, exact */
+  uint64_t slots_or_bits; /* hash slots, or bitmap span in bits */
+  uint64_t bytes;         /* device bytes of the table */
+  int64_t min, max;       /* of the keys; 1 and -1 (min > max) when empty */
+  uint8_t kind;           /* 1 hash, 2 bitmap */
+} obx_keyset_info;
+
+/* kind: 0 auto, 1 hash, 2 bitmap. Duplicates allowed; n == 0 is the empty
+ * set. Returns a set id >= 0 or a negative status (OBX_NOT_SUPPORTED: a
+ * bitmap asked for over a span past the cap). */
+int obx_gpu_keyset_create(obx_gpu_ctx *ctx, const int64_t *keys, uint64_t n,
+                          int kind);
+/* The set of column proj_idx of the handle's last obx_gpu_scan_project
+ * result, built on the device from the result's vector and null flags: NULL
+ * rows are skipped, narrower datums are widened (sign-extended for numeric
+ * types, zero-extended for char). The result stays fetchable, unchanged.
+ * OBX_INVALID_ARGUMENT if there is no result to fetch. */
+int obx_gpu_keyset_from_proj(obx_gpu_ctx *ctx, int handle, uint16_t proj_idx,
+                             int kind);
+int obx_gpu_keyset_free(obx_gpu_ctx *ctx, int set_id);
+int obx_gpu_keyset_info(obx_gpu_ctx *ctx, int set_id, obx_keyset_info *out);
+/* TEST INFRASTRUCTURE: build the table in host memory with the same inline
+ * hash, insert, probe and sizing functions the device runs, then probe it:
+ * hit[i] = 1 iff probe[i] is a key. info and hit may be NULL. No GPU needed,
+ * no HIP call. */
+int obx_gpu_keyset_host_model(const int64_t *keys, uint64_t n, int kind,
+                              const int64_t *probe, uint64_t m, uint8_t *hit,
+                              obx_keyset_info *info);
+
 /* TEST INFRASTRUCTURE: render the hipRTC source the JIT would generate
  * for a plan over a synthetic one-block handle (no GPU needed — codegen
  * and strategy selection are host code). agg == NULL renders the
  * bitmap-filter kernel. Returns source bytes (0 = plan not
- * JIT-eligible), negative on invalid arguments. */
+ * JIT-eligible, or a plan with an OBX_OP_IN_SET leaf: there is no context
+ * here to resolve the set), negative on invalid arguments. */
 int64_t obx_jit_dump_src(const obx_filter_desc *filter,
                          const obx_agg_desc *agg,
                          const obx_col_schema *cols, uint16_t n_cols,

@@ -12,11 +12,16 @@ T_INT, T_INT32, T_DATE, T_CHAR, T_DECIMAL_INT = 5, 4, 19, 23, 50
 
 OP_EQ, OP_LE, OP_LT, OP_GE, OP_GT, OP_NE, OP_BT, OP_IN, OP_NU, OP_NN = range(10)
 OP_BLACK = 10
+OP_IN_SET = 11  # member of a device key set; the set id travels in `lo`
 
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_SUM_PROD2, AGG_SUM_PROD3, AGG_SUM_MUL = range(7)
 
 OBX_SUCCESS = 0
 OBX_BUF_NOT_ENOUGH = -4009
+OBX_INVALID_ARGUMENT = -4002
+OBX_NOT_SUPPORTED = -4007
+
+KS_AUTO, KS_HASH, KS_BITMAP = 0, 1, 2
 
 MAX_GROUPS = 64
 MAX_KEY_BYTES = 16
@@ -55,6 +60,13 @@ BX_AND, BX_OR, BX_NOT = 0x70, 0x71, 0x72
 
 
 TOK_AND, TOK_OR = 128, 129
+
+
+class KeysetInfo(C.Structure):
+    """obx_keyset_info: kind 1 = hash, 2 = bitmap; min > max = empty set."""
+    _fields_ = [("n_keys_in", C.c_uint64), ("n_distinct", C.c_uint64),
+                ("slots_or_bits", C.c_uint64), ("bytes", C.c_uint64),
+                ("min", C.c_int64), ("max", C.c_int64), ("kind", C.c_uint8)]
 
 
 class FilterDesc(C.Structure):
@@ -96,9 +108,9 @@ class AggResult(C.Structure):
 
 
 def make_filter(leaves, prog=None):
-    """leaves: list of dicts {col, op, lo, hi?, in_list?}; prog: optional
-    postfix combine program (ints: leaf index, TOK_AND, TOK_OR); None = AND
-    of all leaves."""
+    """leaves: list of dicts {col, op, lo, hi?, in_list?}, or
+    {col, op=OP_IN_SET, set=<key set id>}; prog: optional postfix combine
+    program (ints: leaf index, TOK_AND, TOK_OR); None = AND of all leaves."""
     f = FilterDesc()
     f.n_leaves = len(leaves)
     if prog:
@@ -123,6 +135,9 @@ def make_filter(leaves, prog=None):
             continue
         f.leaves[i].col = lf["col"]
         f.leaves[i].op = lf["op"]
+        if lf["op"] == OP_IN_SET:
+            f.leaves[i].lo = lf["set"]
+            continue
         f.leaves[i].lo = lf.get("lo", 0)
         f.leaves[i].hi = lf.get("hi", 0)
         il = lf.get("in_list", [])

@@ -8,6 +8,7 @@ HIPCC=${HIPCC:-hipcc}
 python3 - << 'PYEOF'
 for src, out in (("obx_dev.h", "obx_embed_dev_h.inc"),
                  ("obx_dev_common.h", "obx_embed_common_h.inc"),
+                 ("obx_keyset.h", "obx_embed_keyset_h.inc"),
                  ("obx_jit_dev.h", "obx_embed_jit_dev_h.inc")):
     txt = open(src).read()
     assert ')OBXRAW"' not in txt
@@ -21,7 +22,7 @@ PYEOF
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
     -Xarch_host -ftrivial-auto-var-init=zero \
     obx_engine.cpp obx_kernels.hip obx_project.hip obx_cs_load.cpp \
-    obx_cs_kernels.hip \
+    obx_cs_kernels.hip obx_keyset.hip \
     -L/opt/rocm/lib -lhiprtc \
     -o ../libobx.so
 echo "built oceanbase_amd/libobx.so"

@@ -126,13 +126,22 @@ enum {
   OBX_LEAF_RANGE = 3,    /* packed-domain unsigned range [lo,hi], ^invert */
   OBX_LEAF_VALUE = 4,    /* generic in-kernel int64 compare */
   OBX_LEAF_NULL = 5,     /* NU/NN on ext-bit columns: pass = is_null^invert */
+  /* key-set leaves (op 11) on the packed-range family; the row's value is
+     (packed ^ mask) + delta (mod 2^64), mask the xor bias of a signed
+     fixed-width domain as in RANGE */
+  OBX_LEAF_SET_BITS = 6, /* lo = delta - set.min, hi = span - 1:
+                            idx = (packed ^ mask) + lo; idx <= hi && bit(idx)
+                            (a value below min wraps past hi) */
+  OBX_LEAF_SET_HASH = 7, /* lo = delta: probe (packed ^ mask) + lo */
 };
 
 /* global part of a leaf (one per filter leaf, shared by every block) */
 typedef struct dev_leaf {
   int64_t vlo, vhi;     /* VALUE-mode operands (order-mapped for char) */
   uint16_t col;
-  uint8_t op;           /* obx_white_op for VALUE mode (10 = BLACK) */
+  uint8_t op;           /* obx_white_op for VALUE mode (10 = BLACK,
+                           11 = IN_SET: in_list holds the set's
+                           obx_keyset_dev view, obx_keyset.h) */
   uint8_t n_in;
   uint8_t char_len;     /* >0: char column — order-map values before compare
                            (byte-lexicographic, like the oracle's char_key) */

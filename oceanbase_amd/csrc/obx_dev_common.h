@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #endif
 #include "obx_dev.h"
+#include "obx_keyset.h"
 
 
 #define WG 256
@@ -255,12 +256,22 @@ __device__ __forceinline__ leaf_ctx make_leaf_ctx(const dev_block &blk,
   x.cc = make_col_ctx(c, blk_bit);
   x.mask = blf.mask; x.lo = blf.lo; x.hi = blf.hi;
   x.mode = blf.mode; x.invert = blf.invert; x.op = plf.op;
-  /* slow fallback: RLE/exception decode, IN lists, or black programs
-     (operand arrays stay in the global leaf) */
+  /* slow fallback: RLE/exception decode, IN lists, black programs or
+     key-set probes (operand arrays stay in the global leaf) */
   x.slow = (x.cc.kind == 4 ||
             (blf.mode == OBX_LEAF_VALUE &&
-             (plf.op == 7 || plf.op == 10))) ? 1 : 0;
+             (plf.op == 7 || plf.op == 10 || plf.op == 11))) ? 1 : 0;
   return x;
+}
+
+/* SET_BITS / SET_HASH row test on the row's value-plus-delta.
+ * __noinline__: keeps the probe loop's registers off the hot range and
+ * ref-mask loops of the kernels that inline leaf_ctx_match. */
+__device__ __noinline__ bool set_leaf_test(const dev_leaf &plf, uint8_t mode,
+                                           uint64_t v, uint64_t hi) {
+  const obx_keyset_dev ks = obx_leaf_keyset(plf);
+  if (mode == OBX_LEAF_SET_BITS) return obx_ks_bit_test(ks.words, v, hi);
+  return obx_ks_hash_test(ks.words, ks.hi, ks.shift, ks.has_marker, v);
 }
 
 __device__ __forceinline__ bool leaf_ctx_match(const blk_view &bv,
@@ -269,6 +280,17 @@ __device__ __forceinline__ bool leaf_ctx_match(const blk_view &bv,
                                                uint32_t r) {
   switch (x.mode) {
     case OBX_LEAF_NONE: return false;
+    case OBX_LEAF_SET_BITS:
+    case OBX_LEAF_SET_HASH: {
+      if (x.cc.has_ext &&
+          bit_read_at(bv.base, bv.rbase_bit + x.cc.ext_bit +
+                                   (uint64_t)r * x.cc.ext_w, x.cc.ext_w))
+        return false;
+      uint64_t v = (bit_read_at(bv.base, bv.rbase_bit + x.cc.data_bit +
+                                             (uint64_t)r * x.cc.W, x.cc.W) ^
+                    x.mask) + x.lo;
+      return set_leaf_test(plf, x.mode, v, x.hi);
+    }
     case OBX_LEAF_ALL:
       if (x.cc.has_ext &&
           bit_read_at(bv.base, bv.rbase_bit + x.cc.ext_bit +
@@ -604,6 +626,9 @@ __device__ __forceinline__ bool leaf_value_match(const dev_leaf &lf, int64_t v,
   if (lf.op == 8) return isn;
   if (lf.op == 9) return !isn;
   if (isn) return false;
+  /* IN_SET: plain equality on the decoded datum (char keys are the raw
+     zero-extended LE bytes; no order map) */
+  if (lf.op == 11) return obx_keyset_probe(obx_leaf_keyset(lf), v);
   if (lf.char_len) v = dev_char_key(v, lf.char_len);
   switch (lf.op) {
     case 0: return v == lf.vlo;
@@ -648,6 +673,12 @@ __device__ __noinline__ bool leaf_match(const blk_view bv,
       bool isn;
       (void)col_value2(bv, blk, c, r, isn);
       return isn != (bool)blf.invert;
+    }
+    case OBX_LEAF_SET_BITS:
+    case OBX_LEAF_SET_HASH: {
+      if (col_is_null_ext(bv, c, r)) return false;
+      return set_leaf_test(plf, blf.mode,
+                           (col_packed(bv, c, r) ^ blf.mask) + blf.lo, blf.hi);
     }
     default: {
       if (plf.op == 10) return black_match(bv, blk, plf, r);
@@ -822,6 +853,7 @@ __device__ __noinline__ uint64_t build_group_key(
  * classes (0 = never passes, 1 = always passes, 2 = row-dependent);
  * implements the executor tree's constant-result short-circuit
  * (ob_pushdown_filter.cpp:1559-1632) at block granularity. */
+/* (the key-set modes SET_BITS / SET_HASH are row-dependent: class 2) */
 __device__ __forceinline__ uint8_t leaf_class(const dev_block &cur,
                                               const dev_leaf &plf,
                                               const blk_leaf &blf) {

@@ -53,6 +53,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   if (!ctx) return OBX_SUCCESS;
   (void)hipSetDevice(ctx->device);
   ctx->handles.clear(); /* ~obx_handle, while the device is current */
+  ctx->keysets.clear();
   (void)hipStreamDestroy(ctx->stream);
   for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1,
                         ctx->ev_mid, ctx->ev_b0, ctx->ev_b1})
@@ -82,7 +83,7 @@ obx_handle::~obx_handle() {
 
 /* every verb resolves its handle id here: null for a null context, an id
    out of range, or a freed handle */
-static obx_handle *lookup(obx_gpu_ctx *ctx, int handle) {
+obx_handle *obx_handle_lookup(obx_gpu_ctx *ctx, int handle) {
   if (!ctx || handle < 0 || handle >= (int)ctx->handles.size()) return nullptr;
   return ctx->handles[handle].get();
 }
@@ -536,16 +537,18 @@ extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
 }
 
 extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
-  if (!lookup(ctx, handle)) return OBX_INVALID_ARGUMENT;
+  if (!obx_handle_lookup(ctx, handle)) return OBX_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(ctx->device));
   ctx->handles[handle].reset();
   return OBX_SUCCESS;
 }
 
-/* build plan header + device leaves (pure: no HIP calls) */
-static int build_plan(const obx_handle &h, const obx_filter_desc *filter,
-                      const obx_agg_desc *agg, dev_plan_hdr &ph,
-                      dev_leaf pl[OBX_DEV_MAX_LEAVES]) {
+/* build plan header + device leaves (pure: no HIP calls). ctx resolves the
+   set ids of IN_SET leaves; the GPU-free probes pass none, and such a leaf
+   is then an unknown id. */
+static int build_plan(const obx_gpu_ctx *ctx, const obx_handle &h,
+                      const obx_filter_desc *filter, const obx_agg_desc *agg,
+                      dev_plan_hdr &ph, dev_leaf pl[OBX_DEV_MAX_LEAVES]) {
   memset(&ph, 0, sizeof(ph));
   memset(pl, 0, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES);
   uint16_t nl = filter ? filter->n_leaves : 0;
@@ -568,8 +571,17 @@ static int build_plan(const obx_handle &h, const obx_filter_desc *filter,
   for (uint16_t i = 0; i < nl; i++) {
     const obx_filter_leaf *lf = &filter->leaves[i];
     if (lf->col >= h.n_cols) return OBX_INVALID_ARGUMENT;
+    if (lf->op > OBX_OP_IN_SET) return OBX_INVALID_ARGUMENT;
     pl[i].col = lf->col;
     pl[i].op = lf->op;
+    if (lf->op == OBX_OP_IN_SET) {
+      /* the set's device view rides in the leaf's in_list words; keys
+         compare as decoded datums, so no char order map */
+      const obx_keyset *ks = obx_keyset_lookup(ctx, lf->lo);
+      if (!ks) return OBX_INVALID_ARGUMENT;
+      obx_keyset_to_leaf(ks->view, pl[i].in_list);
+      continue;
+    }
     pl[i].vlo = lf->lo;
     pl[i].vhi = lf->hi;
     pl[i].n_in = lf->n_in;
@@ -766,7 +778,7 @@ static int prep_query(obx_gpu_ctx *ctx, obx_handle &h,
                       const obx_filter_desc *filter, const obx_agg_desc *agg,
                       dev_plan_hdr &ph, dev_leaf *pl_out = nullptr) {
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(h, filter, agg, ph, pl);
+  int rc = build_plan(ctx, h, filter, agg, ph, pl);
   if (pl_out) memcpy(pl_out, pl, sizeof(pl));
   if (rc != OBX_SUCCESS) return rc;
   uint16_t nl = ph.n_leaves;
@@ -938,14 +950,14 @@ static int run_filter(obx_gpu_ctx *ctx, obx_handle &h,
 extern "C" int obx_gpu_filter(obx_gpu_ctx *ctx, int handle,
                               const obx_filter_desc *filter,
                               int want_row_ids) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   return run_filter(ctx, *hp, filter, want_row_ids);
 }
 
 extern "C" int obx_gpu_fetch_bitmap(obx_gpu_ctx *ctx, int handle, uint8_t *out,
                                     int64_t cap) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (!h.d_bitmap) return OBX_INVALID_ARGUMENT;
@@ -958,7 +970,7 @@ extern "C" int obx_gpu_fetch_bitmap(obx_gpu_ctx *ctx, int handle, uint8_t *out,
 extern "C" int obx_gpu_fetch_row_ids(obx_gpu_ctx *ctx, int handle,
                                      int32_t *out, int64_t cap,
                                      uint64_t *n_out) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (!h.d_row_ids) return OBX_INVALID_ARGUMENT;
@@ -973,7 +985,7 @@ extern "C" int obx_gpu_fetch_row_ids(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_fetch_blk_counts(obx_gpu_ctx *ctx, int handle,
                                         uint32_t *out, int64_t cap) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (!h.d_blk_counts) return OBX_INVALID_ARGUMENT;
@@ -985,7 +997,7 @@ extern "C" int obx_gpu_fetch_blk_counts(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_decode(obx_gpu_ctx *ctx, int handle,
                               const uint16_t *proj_cols, uint16_t n_proj) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -1041,7 +1053,7 @@ extern "C" int obx_gpu_decode(obx_gpu_ctx *ctx, int handle,
 
 extern "C" int obx_gpu_fetch_col(obx_gpu_ctx *ctx, int handle, uint16_t col,
                                  uint8_t *out, int64_t cap) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (col >= h.n_cols || !h.d_decode_out[col]) return OBX_INVALID_ARGUMENT;
@@ -1073,7 +1085,7 @@ extern "C" int obx_gpu_scan_project(obx_gpu_ctx *ctx, int handle,
                                     const obx_filter_desc *filter,
                                     const uint16_t *proj_cols, uint16_t n_proj,
                                     int want_row_nos, uint64_t *n_rows) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   h.sel_n_proj = 0; /* a failed call leaves no result behind */
@@ -1170,7 +1182,7 @@ extern "C" int obx_gpu_fetch_proj(obx_gpu_ctx *ctx, int handle,
                                   uint64_t count, uint8_t *out, int64_t cap,
                                   uint8_t *out_nulls, int64_t nulls_cap,
                                   uint64_t *n_out) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (proj_idx >= h.sel_n_proj) return OBX_INVALID_ARGUMENT;
@@ -1205,7 +1217,7 @@ extern "C" int obx_gpu_fetch_proj_row_nos(obx_gpu_ctx *ctx, int handle,
                                           uint64_t start, uint64_t count,
                                           uint64_t *out, int64_t cap,
                                           uint64_t *n_out) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   if (!h.sel_n_proj || !h.sel_has_row_nos) return OBX_INVALID_ARGUMENT;
@@ -1230,7 +1242,7 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                                        const obx_filter_desc *filter,
                                        const obx_agg_desc *agg,
                                        obx_agg_result *out) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp || !out) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -1434,6 +1446,9 @@ extern "C" int64_t obx_jit_dump_src_ex(
     uint32_t *grid_out, char *out, int64_t cap) {
   if (!cols || n_cols > OBX_DEV_MAX_COLS) return OBX_INVALID_ARGUMENT;
   if (grid_out) *grid_out = 0;
+  /* no context here to resolve a set id: such a plan renders nothing */
+  for (uint16_t i = 0; filter && i < filter->n_leaves && i < 8; i++)
+    if (filter->leaves[i].op == OBX_OP_IN_SET) return 0;
   obx_handle h;
   h.n_cols = n_cols;
   h.n_blocks = n_blocks ? n_blocks : 1;
@@ -1466,7 +1481,7 @@ extern "C" int64_t obx_jit_dump_src_ex(
   summarize_col_classes(h); /* one synthetic block stands for all */
   dev_plan_hdr ph;
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(h, filter, agg, ph, pl);
+  int rc = build_plan(nullptr, h, filter, agg, ph, pl);
   if (rc != OBX_SUCCESS) return rc;
   if (!agg) { /* bitmap-filter path: dump the wave-per-block filter JIT */
     jit_fstrategy fst;
@@ -1535,7 +1550,7 @@ extern "C" int obx_jit_probe_blocks(
   }
   dev_plan_hdr ph;
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(h, filter, agg, ph, pl);
+  int rc = build_plan(nullptr, h, filter, agg, ph, pl);
   if (rc != OBX_SUCCESS) return rc;
   jit_shape js;
   return jit_plan_shape(ph, js) && jit_blocks_ok(h, ph, js) ? 1 : 0;
@@ -1598,7 +1613,7 @@ extern "C" int obx_gpu_last_bdesc(obx_gpu_ctx *ctx) {
 
 /* how many descriptor arrays this handle has built so far (cache misses) */
 extern "C" int64_t obx_gpu_bdesc_builds(obx_gpu_ctx *ctx, int handle) {
-  obx_handle *h = lookup(ctx, handle);
+  obx_handle *h = obx_handle_lookup(ctx, handle);
   return h ? (int64_t)h->bdesc_builds : -1;
 }
 
@@ -1621,15 +1636,15 @@ extern "C" uint32_t obx_gpu_last_grid(obx_gpu_ctx *ctx) {
 }
 
 extern "C" uint64_t obx_gpu_total_rows(obx_gpu_ctx *ctx, int handle) {
-  const obx_handle *h = lookup(ctx, handle);
+  const obx_handle *h = obx_handle_lookup(ctx, handle);
   return h ? h->total_rows : 0;
 }
 extern "C" uint64_t obx_gpu_total_bytes(obx_gpu_ctx *ctx, int handle) {
-  const obx_handle *h = lookup(ctx, handle);
+  const obx_handle *h = obx_handle_lookup(ctx, handle);
   return h ? h->total_bytes : 0;
 }
 extern "C" uint64_t obx_gpu_last_survivors(obx_gpu_ctx *ctx, int handle) {
-  const obx_handle *h = lookup(ctx, handle);
+  const obx_handle *h = obx_handle_lookup(ctx, handle);
   return h ? h->last_survivors : 0;
 }
 
@@ -1641,7 +1656,7 @@ extern "C" int obx_gpu_agg_fetch(obx_gpu_ctx *ctx, int handle,
                                  uint32_t start, uint32_t count,
                                  obx_group_row *out, uint32_t *n_out,
                                  uint64_t *n_total) {
-  obx_handle *hp = lookup(ctx, handle);
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
   if (!hp || !out) return OBX_INVALID_ARGUMENT;
   obx_handle &h = *hp;
   uint64_t total = h.last_rows.size();

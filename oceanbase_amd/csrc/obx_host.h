@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "obx_dev.h"
+#include "obx_keyset.h"
 #include "obx_project.h"
 
 #define OBX_WG_HOST 256 /* must match the kernels' WG */
@@ -101,6 +102,16 @@ extern "C" __global__ void k_project_sel_lds(
     uint64_t *, uint64_t);
 extern "C" __global__ void k_project_pack_nulls(const uint8_t *, uint64_t,
                                                 uint64_t, uint32_t, uint8_t *);
+
+/* key-set build (obx_keyset.hip): keys are the non-null datums of a dense
+   vector of len-byte datums; nulls == nullptr = none are null. scr words:
+   0 min, 1 max, 2 non-null keys, 3 distinct keys, 4 hash marker flag. */
+extern "C" __global__ void k_keyset_minmax(
+    const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint64_t,
+    unsigned long long *);
+extern "C" __global__ void k_keyset_insert(
+    const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint64_t,
+    uint64_t *, uint64_t, int64_t, uint32_t, uint32_t, unsigned long long *);
 
 #define HIP_TRY(x)                                        \
   do {                                                    \
@@ -242,6 +253,19 @@ struct obx_handle {
   bool col_known[OBX_DEV_MAX_COLS] = {};    /* bounds known in EVERY block */
 };
 
+/* One device-resident key set (obx_keyset.h). Owns its table; lives behind a
+   unique_ptr in the context from build to free / close, like a handle. */
+struct obx_keyset {
+  obx_keyset() = default;
+  obx_keyset(const obx_keyset &) = delete;
+  obx_keyset &operator=(const obx_keyset &) = delete;
+  ~obx_keyset() { if (d_words) (void)hipFree(d_words); }
+
+  uint64_t *d_words = nullptr;
+  obx_keyset_dev view = {};  /* what a set leaf carries to the kernels */
+  obx_keyset_info info = {};
+};
+
 struct obx_gpu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -263,7 +287,16 @@ struct obx_gpu_ctx {
   uint8_t *h_result = nullptr;
   /* a handle's id is its index here: never reused, null once freed */
   std::vector<std::unique_ptr<obx_handle>> handles;
+  /* key sets, same rule: a set's id is its index, null once freed */
+  std::vector<std::unique_ptr<obx_keyset>> keysets;
 };
+
+/* every use of a set id resolves it here (obx_keyset.hip): null for a null
+   context, an id out of range, or a freed set. No HIP call. */
+const obx_keyset *obx_keyset_lookup(const obx_gpu_ctx *ctx, int64_t set_id);
+/* every verb resolves its handle id here (obx_engine.cpp): null for a null
+   context, an id out of range, or a freed handle */
+obx_handle *obx_handle_lookup(obx_gpu_ctx *ctx, int handle);
 
 static inline uint32_t grid_for(uint32_t n_blocks) {
   uint32_t g = n_blocks < 4096u ? n_blocks : 4096u;

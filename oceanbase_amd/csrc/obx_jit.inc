@@ -67,6 +67,9 @@ static const char *OBX_JIT_SRC_COMMON_H =
 static const char *OBX_JIT_SRC_JIT_DEV_H =
 #include "obx_embed_jit_dev_h.inc"
     ;
+static const char *OBX_JIT_SRC_KEYSET_H =
+#include "obx_embed_keyset_h.inc"
+    ;
 
 static std::map<std::string, jit_entry> g_jit_cache;
 static int g_jit_kind = 0; /* 1 = v1 generator, 2 = v2 (persistent) */
@@ -180,11 +183,11 @@ static jit_entry *jit_get(const std::string &key, GenSrc &&gen_src,
     if (f) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
   }
   hiprtcProgram prog;
-  const char *hdrs[3] = {OBX_JIT_SRC_COMMON_H, OBX_JIT_SRC_DEV_H,
-                         OBX_JIT_SRC_JIT_DEV_H};
-  const char *hdr_names[3] = {"obx_dev_common.h", "obx_dev.h",
-                              "obx_jit_dev.h"};
-  if (hiprtcCreateProgram(&prog, src.c_str(), dump_name, 3, hdrs,
+  const char *hdrs[4] = {OBX_JIT_SRC_COMMON_H, OBX_JIT_SRC_DEV_H,
+                         OBX_JIT_SRC_JIT_DEV_H, OBX_JIT_SRC_KEYSET_H};
+  const char *hdr_names[4] = {"obx_dev_common.h", "obx_dev.h",
+                              "obx_jit_dev.h", "obx_keyset.h"};
+  if (hiprtcCreateProgram(&prog, src.c_str(), dump_name, 4, hdrs,
                           hdr_names) != HIPRTC_SUCCESS)
     return nullptr;
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",

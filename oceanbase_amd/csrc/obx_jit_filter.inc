@@ -3,7 +3,10 @@
  * strategy signature, source (included by obx_jit.inc).
  *
  * Eligibility: one to four leaves, each packed-range or dict-mask (the
- * classes of the scan kernel's inline filter). A filter touches only its
+ * classes of the scan kernel's inline filter), or a key-set leaf (IN_SET) on
+ * a packed-range-family column (staged mode only: per field the SET_BITS /
+ * SET_HASH row test of k_lower_leaves against the set's bitmap or hash
+ * table, the set's view loaded once per block). A filter touches only its
  * leaf streams, so neither mode stages whole blocks:
  *  - staged (default when the leaf streams of one block fit 18 KB of LDS;
  *    OBX_JIT_FSTAGE=0 forces the other): workgroup per block, each leaf's
@@ -17,7 +20,9 @@
  */
 
 struct jit_fstrategy {
-  uint8_t leaf_kind[4] = {};  /* 1 = packed range, 2 = dict ref mask */
+  uint8_t leaf_kind[4] = {};  /* 1 = packed range, 2 = dict ref mask,
+                                 3 = key set on a packed-range column */
+  uint8_t leaf_form[4] = {};  /* kind 3: OBX_KS_* form of the set */
   uint16_t leaf_cols[4] = {};
   uint8_t leaf_multi[4] = {}; /* r entries per packed read */
   uint8_t r = 1;              /* rows per lane (strip mining) */
@@ -50,12 +55,20 @@ static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
     st.nslice = (uint8_t)sl;
   }
   uint32_t wmax = 0;
+  bool has_set = false;
   for (uint32_t i = 0; i < ph.n_leaves; i++) {
     uint16_t col = pl[i].col;
     bool mask_ok = pl[i].op != 10 || pl[i].n_bcols == 1;
     if (h.col_dict_any[col] && mask_ok) st.leaf_kind[i] = 2;
     else if (pl[i].op <= 6 && h.col_rangefam_every[col])
       st.leaf_kind[i] = 1;
+    else if (pl[i].op == 11 && h.col_rangefam_every[col]) {
+      /* every block lowers to SET_BITS / SET_HASH (by the set's form) or
+         NONE */
+      st.leaf_kind[i] = 3;
+      st.leaf_form[i] = obx_leaf_keyset(pl[i]).form;
+      has_set = true;
+    }
     else return false;
     st.leaf_cols[i] = col;
     if (h.col_maxw[col] > wmax) wmax = h.col_maxw[col];
@@ -103,8 +116,9 @@ static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
     bool want = !ge || ge[0] != '0';
     if (want && total > 0 && total <= 18u * 1024u) st.fstage = 1;
   }
-  /* combine programs are codegen-folded in the staged kernel only */
-  if (ph.n_prog && !st.fstage) return false;
+  /* combine programs are codegen-folded in the staged kernel only, and
+     only it probes key sets */
+  if ((ph.n_prog || has_set) && !st.fstage) return false;
   return true;
 }
 
@@ -123,8 +137,8 @@ static std::string jit_fstrategy_sig(const dev_plan_hdr &ph,
   }
   k += "|";
   for (uint32_t i = 0; i < ph.n_leaves; i++) {
-    snprintf(b, sizeof b, "L%d:%u:m%d|", st.leaf_kind[i], st.leaf_cols[i],
-             st.leaf_multi[i]);
+    snprintf(b, sizeof b, "L%d:%u:m%d:k%d|", st.leaf_kind[i], st.leaf_cols[i],
+             st.leaf_multi[i], st.leaf_form[i]);
     k += b;
   }
   return k;
@@ -198,8 +212,12 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
              "  unsigned long long lmask[%d];\n"
              "  long long llo[%d], lhi[%d];\n"
              "  uint8_t linv[%d], lall[%d], lnone[%d];\n"
+             "  /* key-set leaves: the set's view */\n"
+             "  const uint64_t *kw[%d];\n"
+             "  uint64_t khi[%d];\n"
+             "  uint32_t kshift[%d], kmark[%d];\n"
              "};\n",
-             NL, NL, NL, NL, NL, NL, NL, NL, NL, NL);
+             NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL);
     s += b;
     s += "__device__ __forceinline__ bool load_params(\n"
          "    const uint8_t *__restrict__ buf,\n"
@@ -250,6 +268,19 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
                "  p.lnone[%d] = bl[%d].mode == OBX_LEAF_NONE ? 1 : 0;\n",
                i, i, i, i, i, i, i, i, i, i, i, i);
       s += b;
+      if (st.leaf_kind[i] == 3) {
+        snprintf(b, sizeof b,
+                 "  {\n"
+                 "    const obx_keyset_dev ks = "
+                 "obx_leaf_keyset(plan_leaves[%d]);\n"
+                 "    p.kw[%d] = ks.words;\n"
+                 "    p.khi[%d] = ks.hi;\n"
+                 "    p.kshift[%d] = ks.shift;\n"
+                 "    p.kmark[%d] = ks.has_marker;\n"
+                 "  }\n",
+                 i, i, i, i, i);
+        s += b;
+      }
     }
     s += "  return true;\n"
          "}\n"
@@ -268,6 +299,34 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
       s += b;
     }
     s += "}\n";
+    /* key-set leaf i (kind 3) over one packed field: the SET_BITS or
+       SET_HASH row test, as `const bool lf<i> = ...` for a combine program
+       or as a step of the AND chain */
+    auto set_stmt = [&](int i, bool multi, bool as_bool) {
+      char t[256];
+      if (multi)
+        snprintf(t, sizeof t, "((wl%d >> (k * cur.W[%d])) & lmk%d)", i, i, i);
+      else
+        snprintf(t, sizeof t,
+                 "jit_bread(seg + %uu, cur.bit[%d] + r * cur.W[%d], "
+                 "cur.W[%d])",
+                 off[i], i, i, i);
+      const std::string n = std::to_string(i);
+      const std::string v = "((" + std::string(t) + " ^ cur.lmask[" + n +
+                            "]) + (uint64_t)cur.llo[" + n + "])";
+      std::string e;
+      if (st.leaf_form[i] == OBX_KS_BITMAP)
+        e = "!cur.lnone[" + n + "] &&\n              obx_ks_bit_test(cur.kw[" +
+            n + "], " + v + ",\n              (uint64_t)cur.lhi[" + n + "])";
+      else if (st.leaf_form[i] == OBX_KS_HASH)
+        e = "!cur.lnone[" + n + "] &&\n              obx_ks_hash_test(cur.kw[" +
+            n + "], cur.khi[" + n + "], cur.kshift[" + n + "],\n"
+            "              cur.kmark[" + n + "], " + v + ")";
+      else
+        e = "false"; /* the empty set */
+      return as_bool ? "          const bool lf" + n + " = " + e + ";\n"
+                     : "          if (live)\n            live = " + e + ";\n";
+    };
     /* sweep of one staged block (emitted inside the block loop below) */
     std::string sweep;
     sweep += "      {\n";
@@ -316,6 +375,10 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
       if (ph.n_prog) {
         sweep += "          if (live) {\n";
         for (int i = 0; i < NL; i++) {
+          if (st.leaf_kind[i] == 3) {
+            sweep += set_stmt(i, st.leaf_multi[i] != 0, true);
+            continue;
+          }
           if (st.leaf_kind[i] == 1) {
             if (st.leaf_multi[i])
               snprintf(b, sizeof b,
@@ -356,6 +419,10 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
                  "          }\n";
       } else {
       for (int i = 0; i < NL; i++) {
+        if (st.leaf_kind[i] == 3) {
+          sweep += set_stmt(i, st.leaf_multi[i] != 0, false);
+          continue;
+        }
         if (st.leaf_kind[i] == 1) {
           if (st.leaf_multi[i])
             snprintf(b, sizeof b,
@@ -435,6 +502,10 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
     if (ph.n_prog) {
       sweep += "        if (live) {\n";
       for (int i = 0; i < NL; i++) {
+        if (st.leaf_kind[i] == 3) {
+          sweep += set_stmt(i, false, true);
+          continue;
+        }
         if (st.leaf_kind[i] == 1)
           snprintf(b, sizeof b,
                    "        uint64_t v%d = jit_bread(seg + %uu, cur.bit[%d]"
@@ -456,6 +527,10 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
                "        }\n";
     } else {
     for (int i = 0; i < NL; i++) {
+      if (st.leaf_kind[i] == 3) {
+        sweep += set_stmt(i, false, false);
+        continue;
+      }
       if (st.leaf_kind[i] == 1)
         snprintf(b, sizeof b,
                  "        if (live && !l%d_all) {\n"

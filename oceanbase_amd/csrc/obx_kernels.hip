@@ -973,6 +973,69 @@ extern "C" __global__ void k_lower_leaves(
      refs live in the exception list, so it takes the VALUE slow path
      (col_value2 walks the exceptions). */
   const bool is_dict = (c.enc == OBX_D_DICT || c.enc == OBX_D_RLE);
+
+  /* key-set membership (IN_SET): a small dict is probed once per entry
+     into a ref mask (the filter-on-dict path; the null ref stays unset); a
+     const column folds to ALL/NONE; the packed-range family tests
+     value = (packed ^ mask) + delta per row against the bitmap or the hash
+     table; everything else probes the decoded value (VALUE mode). The
+     stored min/max only ever proves NONE here, never ALL. */
+  if (lf.op == 11) {
+    const obx_keyset_dev ks = obx_leaf_keyset(lf);
+    uint64_t delta = 0;
+    bool packed_dom = false;
+    if (ks.form == OBX_KS_EMPTY) {
+      o.mode = OBX_LEAF_NONE;
+    } else if (is_dict && c.count < 64) {
+      for (uint32_t e = 0; e < c.count; e++)
+        if (obx_keyset_probe(ks, dict_entry(bv, c, e))) o.mask |= 1ull << e;
+      o.mode = (o.mask == 0) ? OBX_LEAF_NONE : OBX_LEAF_REF_MASK;
+    } else if (c.enc == OBX_D_CONST && c.runs == 0) {
+      o.mode = (c.count != 0 && obx_keyset_probe(ks, c.base)) ? OBX_LEAF_ALL
+                                                              : OBX_LEAF_NONE;
+    } else if (c.enc == OBX_D_RAW && (c.flags & OBX_DF_BITPACK)) {
+      packed_dom = true; /* zero-extended field */
+    } else if (c.enc == OBX_D_RAW && !(c.flags & OBX_DF_STRING)) {
+      /* fixed width: a signed k-byte field is (packed ^ bias) - bias, the
+         order map of the RANGE lowering below */
+      const uint32_t kbits = (uint32_t)c.width * 8;
+      const bool signed_dom =
+          ((c.flags & OBX_DF_SIGNED) && c.width >= c.tss) ||
+          (!(c.flags & OBX_DF_SIGNED) && c.width == 8);
+      if (signed_dom && kbits >= 8 && kbits <= 64) {
+        o.mask = 1ull << (kbits - 1);
+        delta = 0 - o.mask;
+      }
+      packed_dom = true;
+    } else if (c.enc == OBX_D_INTDIFF) {
+      delta = (uint64_t)c.base;
+      packed_dom = true;
+    } else {
+      o.mode = OBX_LEAF_VALUE;
+    }
+    if (packed_dom) {
+      if (ks.form == OBX_KS_BITMAP) {
+        o.mode = OBX_LEAF_SET_BITS;
+        o.lo = delta - (uint64_t)ks.min;
+        o.hi = ks.hi;
+      } else {
+        o.mode = OBX_LEAF_SET_HASH;
+        o.lo = delta;
+      }
+    }
+    if (minmax && !(c.flags & OBX_DF_STRING) &&
+        (o.mode == OBX_LEAF_SET_BITS || o.mode == OBX_LEAF_SET_HASH ||
+         o.mode == OBX_LEAF_VALUE)) {
+      int64_t mn = minmax[2 * ((uint64_t)b * n_cols + lf.col)];
+      int64_t mx = minmax[2 * ((uint64_t)b * n_cols + lf.col) + 1];
+      if (!(mn == INT64_MIN && mx == INT64_MAX) &&
+          (mn > mx || mx < ks.min || mn > ks.max))
+        o.mode = OBX_LEAF_NONE;
+    }
+    out[idx] = o;
+    return;
+  }
+
   if (is_dict && c.count < 64) {
     if (lf.op == 8) {
       o.mask = 1ull << c.count;

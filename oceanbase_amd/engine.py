@@ -86,6 +86,21 @@ def _load():
     lib.obx_gpu_last_bdesc.argtypes = [C.c_void_p]
     lib.obx_gpu_bdesc_builds.restype = C.c_int64
     lib.obx_gpu_bdesc_builds.argtypes = [C.c_void_p, C.c_int]
+    lib.obx_gpu_keyset_create.restype = C.c_int
+    lib.obx_gpu_keyset_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.c_int]
+    lib.obx_gpu_keyset_from_proj.restype = C.c_int
+    lib.obx_gpu_keyset_from_proj.argtypes = [C.c_void_p, C.c_int, C.c_uint16,
+                                             C.c_int]
+    lib.obx_gpu_keyset_free.restype = C.c_int
+    lib.obx_gpu_keyset_free.argtypes = [C.c_void_p, C.c_int]
+    lib.obx_gpu_keyset_info.restype = C.c_int
+    lib.obx_gpu_keyset_info.argtypes = [C.c_void_p, C.c_int,
+                                        C.POINTER(abi.KeysetInfo)]
+    lib.obx_gpu_keyset_host_model.restype = C.c_int
+    lib.obx_gpu_keyset_host_model.argtypes = [
+        C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+        C.POINTER(abi.KeysetInfo)]
     for f in ("obx_gpu_total_rows", "obx_gpu_total_bytes",
               "obx_gpu_last_survivors"):
         getattr(lib, f).restype = C.c_uint64
@@ -101,6 +116,38 @@ def lib():
     if _lib is None:
         _lib = _load()
     return _lib
+
+
+class KeysetError(RuntimeError):
+    """A key-set verb failed; .rc is the engine's status code."""
+
+    def __init__(self, what, rc):
+        super().__init__(f"{what} failed: {rc}")
+        self.rc = rc
+
+
+def _i64(a):
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+
+
+def keyset_host_model(keys, probe=(), kind=0):
+    """TEST INFRASTRUCTURE: build a key set in host memory with the inline
+    functions the device runs and probe it. Needs no GPU. Returns
+    (hit: bool array over probe, abi.KeysetInfo); raises KeysetError with
+    the engine's status (e.g. OBX_NOT_SUPPORTED for a forced bitmap past
+    the span cap)."""
+    import numpy as np
+    k, p = _i64(keys), _i64(probe)
+    hit = np.zeros(p.size, dtype=np.uint8)
+    info = abi.KeysetInfo()
+    rc = lib().obx_gpu_keyset_host_model(
+        k.ctypes.data_as(C.c_void_p), k.size, kind,
+        p.ctypes.data_as(C.c_void_p), p.size,
+        hit.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc != 0:
+        raise KeysetError("obx_gpu_keyset_host_model", rc)
+    return hit.astype(bool), info
 
 
 class GpuEngine:
@@ -143,6 +190,40 @@ class GpuEngine:
 
     def free(self, handle):
         self._lib.obx_gpu_free_blocks(self._ctx, handle)
+
+    # ---- key sets (a join's build keys pushed into the scan) -------------
+    def keyset_create(self, keys, kind=0):
+        """Device key set of int64 keys (duplicates allowed, may be empty);
+        kind 0 auto, 1 hash, 2 bitmap. Returns the set id an
+        abi.OP_IN_SET leaf names (dict(col=c, op=OP_IN_SET, set=sid))."""
+        k = _i64(keys)
+        sid = self._lib.obx_gpu_keyset_create(
+            self._ctx, k.ctypes.data_as(C.c_void_p), k.size, kind)
+        if sid < 0:
+            raise KeysetError("obx_gpu_keyset_create", sid)
+        return sid
+
+    def keyset_from_proj(self, handle, proj_idx, kind=0):
+        """Key set of projected position proj_idx of the handle's last
+        scan_project result, built on the device; NULL rows are skipped and
+        the result stays fetchable."""
+        sid = self._lib.obx_gpu_keyset_from_proj(self._ctx, handle, proj_idx,
+                                                 kind)
+        if sid < 0:
+            raise KeysetError("obx_gpu_keyset_from_proj", sid)
+        return sid
+
+    def keyset_free(self, sid):
+        rc = self._lib.obx_gpu_keyset_free(self._ctx, sid)
+        if rc != 0:
+            raise KeysetError("obx_gpu_keyset_free", rc)
+
+    def keyset_info(self, sid):
+        info = abi.KeysetInfo()
+        rc = self._lib.obx_gpu_keyset_info(self._ctx, sid, C.byref(info))
+        if rc != 0:
+            raise KeysetError("obx_gpu_keyset_info", rc)
+        return info
 
     def filter(self, handle, filter_desc, want_row_ids=False):
         rc = self._lib.obx_gpu_filter(self._ctx, handle,
