@@ -14,11 +14,10 @@ for src, out in (("obx_dev.h", "obx_embed_dev_h.inc"),
     assert ')OBXRAW"' not in txt
     open(out, "w").write('R"OBXRAW(' + txt + ')OBXRAW"\n')
 PYEOF
-# Host code zero-initialises automatic variables that have no initialiser.
-# The JIT cache key (jit_strategy_sig, obx_jit_scan.inc) prints strategy
-# entries past the plan's aggregate count, which nothing else sets: from
-# whatever the stack held, the same plan could miss the cache and compile
-# again inside a query (one ~240 ms step). Device code is not affected.
+# Host code zero-initialises automatic variables that have no initialiser:
+# a safety net, kept until all host code has been audited for reads of
+# unset locals. The JIT strategy structs no longer rely on it (every member
+# has an initialiser). Device code is not affected.
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
     -Xarch_host -ftrivial-auto-var-init=zero \
     obx_engine.cpp obx_kernels.hip obx_project.hip obx_cs_load.cpp \

@@ -1497,16 +1497,11 @@ extern "C" int64_t obx_jit_dump_src_ex(
     }
     return (int64_t)fsrc.size();
   }
-  jit_shape js;
-  if (!jit_plan_shape(ph, js)) return 0;
-  if (!jit_blocks_ok(h, ph, js)) return 0;
-  jit_strategy st;
-  if (!force_v1) jit_build_strategy(h, ph, js, pl, st);
-  if (!st.ok && js.has_mm) return 0; /* v1 cannot do MIN/MAX */
-  if (st.ok && grid_out)
-    *grid_out = jit_grid_for(h.n_blocks, h.n_cus, st.wpb);
-  std::string src = st.ok ? jit_gen_source_v2(ph, js, st)
-                          : jit_gen_source(ph, js);
+  jit_scan_choice c;
+  if (!jit_scan_choose(h, ph, pl, force_v1 != 0, c)) return 0;
+  if (c.kind == 2 && grid_out)
+    *grid_out = jit_grid_for(h.n_blocks, h.n_cus, c.st.wpb);
+  std::string src = jit_scan_source(ph, c);
   if (out && cap > (int64_t)src.size()) {
     memcpy(out, src.data(), src.size());
     out[src.size()] = 0;

@@ -17,14 +17,35 @@
  * bit-identical: the same decode helpers (obx_dev_common.h) and the same
  * exact int128 arithmetic.
  *
- * This file holds what the generators share: the embedded device headers,
- * the compile cache, plan-shape and block eligibility, compile-and-cache,
- * and prepare / launch. The generators themselves, one file per kernel:
+ * This file holds what the generators share: the source emitter, the
+ * packed-stream and leaf-test fragments, the embedded device headers, the
+ * compile cache, plan-shape and block eligibility, compile-and-cache, and
+ * choose / prepare / launch. The generators themselves, one file per kernel:
  *   obx_jit_scan_v1.inc  scan, digit-split window accumulators (fallback
  *                        when the persistent kernel's bounds cannot be proven)
  *   obx_jit_scan.inc     scan, persistent accumulators (the Q1/Q6 hot path)
  *   obx_jit_filter.inc   bitmap / row-id filter
  * Device text that does not depend on the plan is in obx_jit_dev.h.
+ *
+ * Layout of a generator: one function per kernel phase, each with the
+ * signature (plan, shape, strategy, out), and a top-level jit_gen_* that is
+ * the list of those calls in kernel order. All text goes through jit_emit /
+ * jit_fmt, which size their own storage: a fragment cannot be truncated.
+ *
+ * Generators are pure: their text depends only on their arguments, and the
+ * cache key (plan signature + strategy signature) prints every argument
+ * field the text reads. No jit_gen_* function reads the environment. The
+ * environment is read where a strategy is built, and every knob lands in a
+ * strategy field that the signature prints:
+ *   jit_build_strategy   OBX_JIT_V2 (ok), OBX_JIT_JWS (jws_on, jws_member,
+ *                        wa64), OBX_JIT_CTAB (ctab_agg), OBX_JIT_R (r),
+ *                        OBX_JIT_M32 (*_m32), OBX_JIT_STRIPES (stripes),
+ *                        OBX_JIT_WPB (wpb), OBX_JIT_BDESC (bdesc),
+ *                        OBX_JIT_SGRID via jit_grid_for (decides ok only)
+ *   jit_build_fstrategy  OBX_JIT_V2 (eligibility), OBX_JIT_FSL (nslice),
+ *                        OBX_JIT_FR (r, leaf_multi), OBX_JIT_FU (fu),
+ *                        OBX_JIT_FSTAGE (fstage)
+ *   jit_scan_choose      OBX_JIT_WPB for the v1 kernel (jit_v1_strategy.wpb)
  *
  * OBX_JIT=0 disables; OBX_JIT_DUMP=<dir> writes the generated source
  * (obx_jit_src.hip, obx_jit_filter_src.hip) into that directory for offline
@@ -32,8 +53,47 @@
  */
 #include <hip/hiprtc.h>
 
+#include <cstdarg>
 #include <map>
 #include <string>
+
+/* The source emitter: printf onto the end of a std::string. Two passes of
+   vsnprintf, so the text is never cut; the format attribute keeps argument
+   mistakes compile-time warnings. A value that a fragment repeats is passed
+   once and named by position (%1$d). */
+__attribute__((format(printf, 2, 0))) static void jit_vemit(std::string &s,
+                                                            const char *fmt,
+                                                            va_list ap) {
+  va_list ap2;
+  va_copy(ap2, ap);
+  const int n = vsnprintf(nullptr, 0, fmt, ap2);
+  va_end(ap2);
+  if (n <= 0) return;
+  const size_t at = s.size();
+  s.resize(at + (size_t)n + 1);
+  vsnprintf(&s[at], (size_t)n + 1, fmt, ap);
+  s.resize(at + (size_t)n);
+}
+
+__attribute__((format(printf, 2, 3))) static void jit_emit(std::string &s,
+                                                           const char *fmt,
+                                                           ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  jit_vemit(s, fmt, ap);
+  va_end(ap);
+}
+
+/* the same, as a value: for text that another fragment embeds */
+__attribute__((format(printf, 1, 2))) static std::string jit_fmt(
+    const char *fmt, ...) {
+  std::string s;
+  va_list ap;
+  va_start(ap, fmt);
+  jit_vemit(s, fmt, ap);
+  va_end(ap);
+  return s;
+}
 
 struct jit_entry {
   hipModule_t mod = nullptr;
@@ -51,7 +111,86 @@ struct jit_shape {
   uint8_t agg_f2 = 0;                /* bit a: PROD2 fused with PROD3 mate */
   bool has_mm = false;               /* MIN/MAX present: v2-only (the v1
                                         generator has no CAS cells) */
+  /* value slot (vcol index) of a plan need index; -1 when there is none */
+  int slot(const dev_plan_hdr &ph, uint8_t need_idx) const {
+    if (need_idx == 0xFF) return -1;
+    for (int j = 0; j < n_vc; j++)
+      if (vcol[j] == ph.need_cols[need_idx]) return j;
+    return -1;
+  }
 };
+
+/* how a filter leaf is evaluated inline, from the load-time column facts;
+   the scan kernel takes the first two, the filter kernel all three */
+enum { JL_NONE = 0, JL_RANGE = 1, JL_MASK = 2, JL_SET = 3 };
+static uint8_t jit_leaf_kind(const obx_handle &h, const dev_leaf &lf) {
+  /* multi-column black programs cannot lower to a ref mask */
+  const bool mask_ok = lf.op != OBX_OP_BLACK || lf.n_bcols == 1;
+  if (h.col_dict_any[lf.col] && mask_ok) return JL_MASK;
+  if (!h.col_rangefam_every[lf.col]) return JL_NONE;
+  if (lf.op <= OBX_OP_BT) return JL_RANGE;
+  return lf.op == OBX_OP_IN_SET ? JL_SET : JL_NONE;
+}
+
+/* A bit-packed stream as the generated code names it: the word that holds
+   the lane's packed fields (w), the width (W) and field mask (m), and for a
+   field read on its own the base pointer and bit offset. */
+struct jit_stream {
+  std::string w, W, m, base, off;
+  /* field k of the lane's strip: cut from the packed word, or read alone */
+  std::string field(bool packed) const {
+    return packed ? jit_fmt("((%s >> (k * %s)) & %s)", w.c_str(), W.c_str(),
+                            m.c_str())
+                  : jit_fmt("jit_bread(%1$s, %2$s + r * %3$s, %3$s)",
+                            base.c_str(), off.c_str(), W.c_str());
+  }
+};
+
+/* names of a lowered leaf's operands, and the two row tests over a field.
+   `pad` is the statement's indent. The chain form narrows `live`; the
+   value form (combine programs) defines `lf<i>`. */
+struct jit_leaf_ops {
+  int i;
+  std::string mask, lo, hi, inv, none;
+};
+
+static void jit_emit_range_test(std::string &s, int pad,
+                                const jit_leaf_ops &o,
+                                const std::string &field, bool chain) {
+  const std::string in(pad, ' ');
+  if (chain)
+    jit_emit(s,
+             "%1$sif (live && !l%2$d_all) {\n"
+             "%1$s  uint64_t v = %3$s ^ %4$s;\n"
+             "%1$s  live = ((v - %5$s) <= (%6$s - %5$s)) != (bool)%7$s;\n"
+             "%1$s}\n",
+             in.c_str(), o.i, field.c_str(), o.mask.c_str(), o.lo.c_str(),
+             o.hi.c_str(), o.inv.c_str());
+  else
+    jit_emit(s,
+             "%1$suint64_t v%2$d = %3$s ^ %4$s;\n"
+             "%1$sconst bool lf%2$d = !%8$s &&\n"
+             "%1$s    (l%2$d_all || (((v%2$d - %5$s) <= (%6$s - %5$s)) != "
+             "(bool)%7$s));\n",
+             in.c_str(), o.i, field.c_str(), o.mask.c_str(), o.lo.c_str(),
+             o.hi.c_str(), o.inv.c_str(), o.none.c_str());
+}
+
+static void jit_emit_mask_test(std::string &s, int pad, const jit_leaf_ops &o,
+                               const std::string &field, bool chain) {
+  const std::string in(pad, ' ');
+  if (chain)
+    jit_emit(s,
+             "%1$sif (live)\n"
+             "%1$s  live = (%2$s >>\n"
+             "%1$s          (uint32_t)%3$s) & 1;\n",
+             in.c_str(), o.mask.c_str(), field.c_str());
+  else
+    jit_emit(s,
+             "%1$sconst bool lf%4$d = (%2$s >>\n"
+             "%1$s    (uint32_t)%3$s) & 1;\n",
+             in.c_str(), o.mask.c_str(), field.c_str(), o.i);
+}
 
 /* the generators: (plan, strategy) -> strategy signature and HIP source */
 #include "obx_jit_scan_v1.inc"
@@ -218,28 +357,54 @@ static jit_entry *jit_get(const std::string &key, GenSrc &&gen_src,
   return &ent;
 }
 
+/* Which scan kernel a plan gets, and everything its generator takes: the
+   one sequence shape -> blocks -> strategy -> v1 or v2 behind both
+   jit_prepare and the dump probe (obx_jit_dump_src_ex). */
+struct jit_scan_choice {
+  int kind = 0; /* 0 = no generated kernel, 1 = v1, 2 = v2 (persistent) */
+  jit_shape js;
+  jit_strategy st;    /* kind 2 */
+  jit_v1_strategy v1; /* kind 1 */
+};
+
+static int jit_scan_choose(const obx_handle &h, const dev_plan_hdr &ph,
+                           const dev_leaf *pl, bool force_v1,
+                           jit_scan_choice &c) {
+  if (!jit_plan_shape(ph, c.js) || !jit_blocks_ok(h, ph, c.js)) return 0;
+  if (!force_v1) jit_build_strategy(h, ph, c.js, pl, c.st); /* !ok -> v1 */
+  if (!c.st.ok && c.js.has_mm) return 0; /* v1 cannot do MIN/MAX */
+  if (!c.st.ok)
+    if (const char *w = getenv("OBX_JIT_WPB")) c.v1.wpb = w;
+  return c.kind = c.st.ok ? 2 : 1;
+}
+
+static std::string jit_scan_key(const dev_plan_hdr &ph,
+                                const jit_scan_choice &c) {
+  return jit_plan_sig(ph) +
+         (c.kind == 2 ? jit_strategy_sig(ph, c.st) : jit_v1_sig(c.v1));
+}
+
+static std::string jit_scan_source(const dev_plan_hdr &ph,
+                                   const jit_scan_choice &c) {
+  return c.kind == 2 ? jit_gen_source_v2(ph, c.js, c.st)
+                     : jit_gen_source(ph, c.js, c.v1);
+}
+
 /* prepare (compile/lookup) before the timed region; nullptr = use the
    precompiled kernels */
 static jit_entry *jit_prepare(const obx_handle &h, const dev_plan_hdr &ph,
                               const dev_leaf *pl) {
   const char *e = getenv("OBX_JIT");
   if (e && e[0] == '0') return nullptr;
-  jit_shape js;
-  if (!jit_plan_shape(ph, js)) return nullptr;
-  if (!jit_blocks_ok(h, ph, js)) return nullptr;
-  jit_strategy st;
-  jit_build_strategy(h, ph, js, pl, st); /* !ok -> v1 generator */
-  if (!st.ok && js.has_mm) return nullptr; /* v1 cannot do MIN/MAX */
-  g_jit_kind = st.ok ? 2 : 1;
+  jit_scan_choice c;
+  if (!jit_scan_choose(h, ph, pl, false, c)) return nullptr;
+  g_jit_kind = c.kind;
   jit_entry *je = jit_get(
-      jit_plan_sig(ph) + (st.ok ? jit_strategy_sig(st) : "V1|"),
-      [&] {
-        return st.ok ? jit_gen_source_v2(ph, js, st) : jit_gen_source(ph, js);
-      },
-      "k_jit_scan", "obx_jit_src.hip", st.ok ? st.wpb : 0);
-  if (je && st.ok) { /* the signature carries both: same for every hit */
-    je->bdesc = st.bdesc != 0;
-    je->bd_cols = st.bd_cols;
+      jit_scan_key(ph, c), [&] { return jit_scan_source(ph, c); },
+      "k_jit_scan", "obx_jit_src.hip", c.kind == 2 ? c.st.wpb : 0);
+  if (je && c.kind == 2) { /* the signature carries both: same for every hit */
+    je->bdesc = c.st.bdesc != 0;
+    je->bd_cols = c.st.bd_cols;
   }
   return je;
 }

@@ -17,12 +17,19 @@
  * Both strip-mine FR rows per lane when FR * width <= 64, assemble the
  * survivor mask in LDS and write the bitmap with two atomicOr per 64 rows.
  * OBX_JIT_FSL / OBX_JIT_FR / OBX_JIT_FU override slices, FR and FU.
+ *
+ * Layout: jit_build_fstrategy (the only place that reads the environment),
+ * jit_fstrategy_sig, the fragments both modes share (combine-program fold,
+ * stream and operand names per mode; the row tests themselves are in
+ * obx_jit.inc), then the phases (plan, strategy, out): prologue; staged
+ * parameters, sweep and kernel; direct kernel. jit_gen_source_filter lists
+ * them.
  */
 
 struct jit_fstrategy {
-  uint8_t leaf_kind[4] = {};  /* 1 = packed range, 2 = dict ref mask,
-                                 3 = key set on a packed-range column */
-  uint8_t leaf_form[4] = {};  /* kind 3: OBX_KS_* form of the set */
+  uint8_t leaf_kind[4] = {};  /* JL_RANGE, JL_MASK, or JL_SET: key set on a
+                                 packed-range column */
+  uint8_t leaf_form[4] = {};  /* JL_SET: OBX_KS_* form of the set */
   uint16_t leaf_cols[4] = {};
   uint8_t leaf_multi[4] = {}; /* r entries per packed read */
   uint8_t r = 1;              /* rows per lane (strip mining) */
@@ -57,19 +64,15 @@ static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
   uint32_t wmax = 0;
   bool has_set = false;
   for (uint32_t i = 0; i < ph.n_leaves; i++) {
-    uint16_t col = pl[i].col;
-    bool mask_ok = pl[i].op != 10 || pl[i].n_bcols == 1;
-    if (h.col_dict_any[col] && mask_ok) st.leaf_kind[i] = 2;
-    else if (pl[i].op <= 6 && h.col_rangefam_every[col])
-      st.leaf_kind[i] = 1;
-    else if (pl[i].op == 11 && h.col_rangefam_every[col]) {
+    const uint16_t col = pl[i].col;
+    st.leaf_kind[i] = jit_leaf_kind(h, pl[i]);
+    if (st.leaf_kind[i] == JL_NONE) return false;
+    if (st.leaf_kind[i] == JL_SET) {
       /* every block lowers to SET_BITS / SET_HASH (by the set's form) or
          NONE */
-      st.leaf_kind[i] = 3;
       st.leaf_form[i] = obx_leaf_keyset(pl[i]).form;
       has_set = true;
     }
-    else return false;
     st.leaf_cols[i] = col;
     if (h.col_maxw[col] > wmax) wmax = h.col_maxw[col];
   }
@@ -124,536 +127,514 @@ static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
 
 static std::string jit_fstrategy_sig(const dev_plan_hdr &ph,
                                      const jit_fstrategy &st) {
-  char b[128];
   std::string k = "F|";
-  snprintf(b, sizeof b, "s%d|r%d|u%d|g%d:%u:%u:%u:%u|i%d:%u|", st.nslice,
-           st.r, st.fu, st.fstage, st.fseg[0], st.fseg[1], st.fseg[2],
-           st.fseg[3], st.frid, (unsigned)st.fnch);
-  k += b;
+  jit_emit(k, "s%d|r%d|u%d|g%d:%u:%u:%u:%u|i%d:%u|", st.nslice, st.r, st.fu,
+           st.fstage, st.fseg[0], st.fseg[1], st.fseg[2], st.fseg[3], st.frid,
+           (unsigned)st.fnch);
   k += "P";
-  for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) {
-    snprintf(b, sizeof b, "%u.", ph.prog[p2]);
-    k += b;
-  }
+  for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) jit_emit(k, "%u.", ph.prog[p2]);
   k += "|";
-  for (uint32_t i = 0; i < ph.n_leaves; i++) {
-    snprintf(b, sizeof b, "L%d:%u:m%d:k%d|", st.leaf_kind[i], st.leaf_cols[i],
+  for (uint32_t i = 0; i < ph.n_leaves; i++)
+    jit_emit(k, "L%d:%u:m%d:k%d|", st.leaf_kind[i], st.leaf_cols[i],
              st.leaf_multi[i], st.leaf_form[i]);
-    k += b;
-  }
   return k;
 }
 
-static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
-                                         const jit_fstrategy &st) {
-  const int NL = ph.n_leaves;
-  char b[1024];
-  std::string s;
+/* ---- fragments the phases share ---- */
+
+/* Codegen fold of the postfix combine program (plan data, so the kernel
+   gets one closed-form expression) over the items <name><leaf>: boolean
+   (&&, ||) for the row test, three-valued (f3and, f3or) for the block
+   verdict. No program = AND of all leaves. */
+static std::string jit_f_fold_prog(const dev_plan_hdr &ph, const char *name,
+                                   bool boolean) {
+  auto item = [&](int i) { return name + std::to_string(i); };
+  if (ph.n_prog == 0) {
+    std::string e = boolean ? "(" : "";
+    for (int i = 0; i < (int)ph.n_leaves; i++) {
+      if (boolean) {
+        if (i) e += " && ";
+        e += item(i);
+      } else {
+        e = i == 0 ? item(i) : ("f3and(" + e + ", " + item(i) + ")");
+      }
+    }
+    if (boolean) e += ")";
+    return e;
+  }
+  std::string stk[16];
+  int sp = 0;
+  for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) {
+    const uint8_t tok = ph.prog[p2];
+    if (tok < ph.n_leaves) {
+      stk[sp++] = item(tok);
+      continue;
+    }
+    const std::string b2 = stk[--sp], a2 = stk[sp - 1];
+    if (boolean)
+      stk[sp - 1] = "(" + a2 + (tok == 128 ? " && " : " || ") + b2 + ")";
+    else
+      stk[sp - 1] = (tok == 128 ? "f3and(" : "f3or(") + a2 + ", " + b2 + ")";
+  }
+  return stk[0];
+}
+
+/* staged mode: byte offset of leaf i's segment in the LDS buffer */
+static uint32_t jit_f_seg_off(const jit_fstrategy &st, int i) {
+  uint32_t off = 0;
+  for (int q = 0; q < i; q++) off += st.fseg[q];
+  return off;
+}
+
+/* leaf i's packed stream and lowered operands, as each mode names them:
+   staged reads its LDS segment and the blkp in registers, direct reads the
+   block in global memory and the blk_leaf (sfx: the pipelined tile) */
+static jit_stream jit_f_staged_stream(const jit_fstrategy &st, int i) {
+  return {jit_fmt("wl%d", i), jit_fmt("cur.W[%d]", i), jit_fmt("lmk%d", i),
+          jit_fmt("seg + %uu", jit_f_seg_off(st, i)),
+          jit_fmt("cur.bit[%d]", i)};
+}
+static jit_leaf_ops jit_f_staged_ops(int i) {
+  return {i,
+          jit_fmt("cur.lmask[%d]", i),
+          jit_fmt("cur.llo[%d]", i),
+          jit_fmt("cur.lhi[%d]", i),
+          jit_fmt("cur.linv[%d]", i),
+          jit_fmt("cur.lnone[%d]", i)};
+}
+static jit_stream jit_f_direct_stream(int i, const char *sfx) {
+  return {jit_fmt("wl%d%s", i, sfx), jit_fmt("l%dW", i), jit_fmt("lmk%d", i),
+          "bp", jit_fmt("l%do", i)};
+}
+static jit_leaf_ops jit_f_direct_ops(int i) {
+  return {i,
+          jit_fmt("lb%d.mask", i),
+          jit_fmt("lb%d.lo", i),
+          jit_fmt("lb%d.hi", i),
+          jit_fmt("lb%d.invert", i),
+          ""};
+}
+
+/* key-set leaf i (JL_SET) over one packed field: the SET_BITS or SET_HASH
+   row test, as `const bool lf<i> = ...` for a combine program or as a step
+   of the AND chain */
+static std::string jit_f_set_test(const jit_fstrategy &st, int i,
+                                  const std::string &field, bool chain) {
+  const std::string n = std::to_string(i);
+  const std::string v = "((" + field + " ^ cur.lmask[" + n +
+                        "]) + (uint64_t)cur.llo[" + n + "])";
+  std::string e;
+  if (st.leaf_form[i] == OBX_KS_BITMAP)
+    e = "!cur.lnone[" + n + "] &&\n              obx_ks_bit_test(cur.kw[" +
+        n + "], " + v + ",\n              (uint64_t)cur.lhi[" + n + "])";
+  else if (st.leaf_form[i] == OBX_KS_HASH)
+    e = "!cur.lnone[" + n + "] &&\n              obx_ks_hash_test(cur.kw[" +
+        n + "], cur.khi[" + n + "], cur.kshift[" + n + "],\n"
+        "              cur.kmark[" + n + "], " + v + ")";
+  else
+    e = "false"; /* the empty set */
+  return chain ? "          if (live)\n            live = " + e + ";\n"
+               : "          const bool lf" + n + " = " + e + ";\n";
+}
+
+/* staged mode: every leaf's test of row r (field k of the packed words
+   when `packed`), narrowing `live`; a combine program evaluates all leaves
+   and folds them */
+static void jit_f_staged_tests(const dev_plan_hdr &ph,
+                               const jit_fstrategy &st, int pad, bool packed,
+                               std::string &s) {
+  const bool chain = ph.n_prog == 0;
+  const std::string in(pad, ' ');
+  if (!chain) s += in + "if (live) {\n";
+  for (int i = 0; i < (int)ph.n_leaves; i++) {
+    const std::string f =
+        jit_f_staged_stream(st, i).field(packed && st.leaf_multi[i]);
+    if (st.leaf_kind[i] == JL_SET)
+      s += jit_f_set_test(st, i, f, chain);
+    else if (st.leaf_kind[i] == JL_RANGE)
+      jit_emit_range_test(s, pad, jit_f_staged_ops(i), f, chain);
+    else
+      jit_emit_mask_test(s, pad, jit_f_staged_ops(i), f, chain);
+  }
+  if (!chain)
+    s += in + "live = " + jit_f_fold_prog(ph, "lf", true) + ";\n" + in +
+         "}\n";
+}
+
+/* direct mode: the AND chain over row r */
+static void jit_f_direct_tests(const dev_plan_hdr &ph,
+                               const jit_fstrategy &st, int pad,
+                               const char *sfx, bool packed, std::string &s) {
+  for (int i = 0; i < (int)ph.n_leaves; i++) {
+    const std::string f =
+        jit_f_direct_stream(i, sfx).field(packed && st.leaf_multi[i]);
+    if (st.leaf_kind[i] == JL_RANGE)
+      jit_emit_range_test(s, pad, jit_f_direct_ops(i), f, true);
+    else
+      jit_emit_mask_test(s, pad, jit_f_direct_ops(i), f, true);
+  }
+}
+
+/* ---- kernel phases ---- */
+
+static void jit_f_prologue(const dev_plan_hdr &ph, const jit_fstrategy &st,
+                           std::string &s) {
   s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
        "#include \"obx_jit_dev.h\"\n\n";
-  snprintf(b, sizeof b,
+  jit_emit(s,
            "#define NL %d\n#define FSL %d\n#define FR %d\n"
            "#define RID %d\n#define NCH %u\n",
-           NL, st.nslice > 0 ? st.nslice : 1, st.r > 0 ? st.r : 1,
-           st.frid ? 1 : 0, (unsigned)(st.fnch ? st.fnch : 1));
-  s += b;
-  /* codegen folds of the postfix combine program (plan data, so the
-     kernel gets one closed-form expression) */
-  auto fold_prog = [&](const char *item_fmt, bool boolean) {
-    char t[96];
-    if (ph.n_prog == 0) {
-      std::string e = boolean ? "(" : "";
-      for (int i2 = 0; i2 < NL; i2++) {
-        snprintf(t, sizeof t, item_fmt, i2);
-        if (boolean) {
-          if (i2) e += " && ";
-          e += t;
-        } else {
-          e = i2 == 0 ? t : ("f3and(" + e + ", " + t + ")");
-        }
-      }
-      if (boolean) e += ")";
-      return e;
-    }
-    std::string stk[16];
-    int sp = 0;
-    for (uint32_t p2 = 0; p2 < ph.n_prog; p2++) {
-      uint8_t tok = ph.prog[p2];
-      if (tok < ph.n_leaves) {
-        snprintf(t, sizeof t, item_fmt, (int)tok);
-        stk[sp++] = t;
-      } else {
-        std::string b2 = stk[--sp], a2 = stk[sp - 1];
-        if (boolean)
-          stk[sp - 1] =
-              "(" + a2 + (tok == 128 ? " && " : " || ") + b2 + ")";
-        else
-          stk[sp - 1] = (tok == 128 ? "f3and(" : "f3or(") + a2 + ", " +
-                        b2 + ")";
-      }
-    }
-    return stk[0];
-  };
-  if (st.fstage) {
-    /* ---- staged mode: WG per block, leaf streams DMA'd to one LDS
-       buffer (the LDS-DMA destination stays uniform + lane-linear) ---- */
-    uint32_t off[4] = {}, total = 0;
-    for (int i = 0; i < NL; i++) { off[i] = total; total += st.fseg[i]; }
-    snprintf(b, sizeof b, "#define SEGSZ %uu\n", total);
-    s += b;
-    s += "struct blkp {\n"
-         "  const uint8_t *bp;\n"
-         "  uint64_t row0;\n"
-         "  uint32_t blk, rows;\n";
-    snprintf(b, sizeof b,
-             "  uint32_t W[%d], bit[%d], lo[%d], len[%d];\n"
-             "  /* leaf payload in registers: loaded once per block, so\n"
-             "     the sweep issues no global load of its own */\n"
-             "  unsigned long long lmask[%d];\n"
-             "  long long llo[%d], lhi[%d];\n"
-             "  uint8_t linv[%d], lall[%d], lnone[%d];\n"
-             "  /* key-set leaves: the set's view */\n"
-             "  const uint64_t *kw[%d];\n"
-             "  uint64_t khi[%d];\n"
-             "  uint32_t kshift[%d], kmark[%d];\n"
-             "};\n",
-             NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL, NL);
-    s += b;
-    s += "__device__ __forceinline__ bool load_params(\n"
-         "    const uint8_t *__restrict__ buf,\n"
-         "    const dev_block *__restrict__ blocks,\n"
-         "    const dev_leaf *__restrict__ plan_leaves,\n"
-         "    const blk_leaf *__restrict__ bleaves, uint32_t blk,\n"
-         "    blkp &p) {\n"
-         "  const dev_block &cur = blocks[blk];\n"
-         "  const blk_leaf *bl = bleaves + (size_t)blk * NL;\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  const uint8_t c%d = leaf_class(cur, plan_leaves[%d], "
-               "bl[%d]);\n",
-               i, i, i);
-      s += b;
-    }
-    s += "  if ((" + fold_prog("c%d", false) + ") == 0) return false;\n";
-    s += ""
-         "  p.blk = blk;\n"
-         "  p.rows = cur.row_count;\n"
-         "  p.row0 = dev_block_row_start(&cur);\n"
-         "  p.bp = buf + cur.block_byte;\n"
-         "  const uint64_t blk_bit = cur.block_byte * 8;\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
+           (int)ph.n_leaves, st.nslice > 0 ? st.nslice : 1,
+           st.r > 0 ? st.r : 1, st.frid ? 1 : 0,
+           (unsigned)(st.fnch ? st.fnch : 1));
+}
+
+/* staged mode: per-block parameters in registers (blkp, load_params) and
+   the LDS DMA of the leaf streams (issue_stage). One LDS buffer: the
+   LDS-DMA destination stays uniform + lane-linear. */
+static void jit_f_staged_params(const dev_plan_hdr &ph,
+                                const jit_fstrategy &st, std::string &s) {
+  const int NL = ph.n_leaves;
+  jit_emit(s, "#define SEGSZ %uu\n", jit_f_seg_off(st, NL));
+  s += "struct blkp {\n"
+       "  const uint8_t *bp;\n"
+       "  uint64_t row0;\n"
+       "  uint32_t blk, rows;\n";
+  jit_emit(s,
+           "  uint32_t W[%1$d], bit[%1$d], lo[%1$d], len[%1$d];\n"
+           "  /* leaf payload in registers: loaded once per block, so\n"
+           "     the sweep issues no global load of its own */\n"
+           "  unsigned long long lmask[%1$d];\n"
+           "  long long llo[%1$d], lhi[%1$d];\n"
+           "  uint8_t linv[%1$d], lall[%1$d], lnone[%1$d];\n"
+           "  /* key-set leaves: the set's view */\n"
+           "  const uint64_t *kw[%1$d];\n"
+           "  uint64_t khi[%1$d];\n"
+           "  uint32_t kshift[%1$d], kmark[%1$d];\n"
+           "};\n",
+           NL);
+  s += "__device__ __forceinline__ bool load_params(\n"
+       "    const uint8_t *__restrict__ buf,\n"
+       "    const dev_block *__restrict__ blocks,\n"
+       "    const dev_leaf *__restrict__ plan_leaves,\n"
+       "    const blk_leaf *__restrict__ bleaves, uint32_t blk,\n"
+       "    blkp &p) {\n"
+       "  const dev_block &cur = blocks[blk];\n"
+       "  const blk_leaf *bl = bleaves + (size_t)blk * NL;\n";
+  for (int i = 0; i < NL; i++)
+    jit_emit(s,
+             "  const uint8_t c%1$d = leaf_class(cur, plan_leaves[%1$d], "
+             "bl[%1$d]);\n",
+             i);
+  s += "  if ((" + jit_f_fold_prog(ph, "c", false) + ") == 0) return false;\n";
+  s += "  p.blk = blk;\n"
+       "  p.rows = cur.row_count;\n"
+       "  p.row0 = dev_block_row_start(&cur);\n"
+       "  p.bp = buf + cur.block_byte;\n"
+       "  const uint64_t blk_bit = cur.block_byte * 8;\n";
+  for (int i = 0; i < NL; i++)
+    jit_emit(s,
+             "  {\n"
+             "    const uint32_t o = (uint32_t)(cur.cols[%1$u].data_bit - "
+             "blk_bit);\n"
+             "    const uint32_t W = PW(cur.cols[%1$u]);\n"
+             "    const uint32_t lo = (o >> 3) & ~15u;\n"
+             "    p.W[%2$d] = W;\n"
+             "    p.lo[%2$d] = lo;\n"
+             "    p.bit[%2$d] = o - lo * 8;\n"
+             "    p.len[%2$d] = ((((o + p.rows * W + 7) >> 3) - lo) + 15) & "
+             "~15u;\n"
+             "  }\n",
+             (unsigned)st.leaf_cols[i], i);
+  for (int i = 0; i < NL; i++) {
+    jit_emit(s,
+             "  p.lmask[%1$d] = bl[%1$d].mask;\n"
+             "  p.llo[%1$d] = bl[%1$d].lo;\n"
+             "  p.lhi[%1$d] = bl[%1$d].hi;\n"
+             "  p.linv[%1$d] = bl[%1$d].invert;\n"
+             "  p.lall[%1$d] = bl[%1$d].mode == OBX_LEAF_ALL ? 1 : 0;\n"
+             "  p.lnone[%1$d] = bl[%1$d].mode == OBX_LEAF_NONE ? 1 : 0;\n",
+             i);
+    if (st.leaf_kind[i] == JL_SET)
+      jit_emit(s,
                "  {\n"
-               "    const uint32_t o = (uint32_t)(cur.cols[%u].data_bit - "
-               "blk_bit);\n"
-               "    const uint32_t W = PW(cur.cols[%u]);\n"
-               "    const uint32_t lo = (o >> 3) & ~15u;\n"
-               "    p.W[%d] = W;\n"
-               "    p.lo[%d] = lo;\n"
-               "    p.bit[%d] = o - lo * 8;\n"
-               "    p.len[%d] = ((((o + p.rows * W + 7) >> 3) - lo) + 15) & "
-               "~15u;\n"
+               "    const obx_keyset_dev ks = "
+               "obx_leaf_keyset(plan_leaves[%1$d]);\n"
+               "    p.kw[%1$d] = ks.words;\n"
+               "    p.khi[%1$d] = ks.hi;\n"
+               "    p.kshift[%1$d] = ks.shift;\n"
+               "    p.kmark[%1$d] = ks.has_marker;\n"
                "  }\n",
-               (unsigned)st.leaf_cols[i], (unsigned)st.leaf_cols[i], i, i,
-               i, i);
-      s += b;
-    }
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  p.lmask[%d] = bl[%d].mask;\n"
-               "  p.llo[%d] = bl[%d].lo;\n"
-               "  p.lhi[%d] = bl[%d].hi;\n"
-               "  p.linv[%d] = bl[%d].invert;\n"
-               "  p.lall[%d] = bl[%d].mode == OBX_LEAF_ALL ? 1 : 0;\n"
-               "  p.lnone[%d] = bl[%d].mode == OBX_LEAF_NONE ? 1 : 0;\n",
-               i, i, i, i, i, i, i, i, i, i, i, i);
-      s += b;
-      if (st.leaf_kind[i] == 3) {
-        snprintf(b, sizeof b,
-                 "  {\n"
-                 "    const obx_keyset_dev ks = "
-                 "obx_leaf_keyset(plan_leaves[%d]);\n"
-                 "    p.kw[%d] = ks.words;\n"
-                 "    p.khi[%d] = ks.hi;\n"
-                 "    p.kshift[%d] = ks.shift;\n"
-                 "    p.kmark[%d] = ks.has_marker;\n"
-                 "  }\n",
-                 i, i, i, i, i);
-        s += b;
-      }
-    }
-    s += "  return true;\n"
-         "}\n"
-         "__device__ __forceinline__ void issue_stage(\n"
-         "    const blkp &p, uint8_t *dst, uint32_t tid) {\n";
-    for (int i = 0; i < NL; i++) {
-      snprintf(b, sizeof b,
-               "  for (uint32_t i2 = tid; i2 * 16 < p.len[%d]; i2 += WG)\n"
-               "    __builtin_amdgcn_global_load_lds(\n"
-               "        (const __attribute__((address_space(1))) uint32_t\n"
-               "             *)(p.bp + p.lo[%d] + (size_t)i2 * 16),\n"
-               "        (__attribute__((address_space(3))) uint32_t\n"
-               "             *)(dst + %uu + (size_t)i2 * 16),\n"
-               "        16, 0, 0);\n",
-               i, i, off[i]);
-      s += b;
-    }
-    s += "}\n";
-    /* key-set leaf i (kind 3) over one packed field: the SET_BITS or
-       SET_HASH row test, as `const bool lf<i> = ...` for a combine program
-       or as a step of the AND chain */
-    auto set_stmt = [&](int i, bool multi, bool as_bool) {
-      char t[256];
-      if (multi)
-        snprintf(t, sizeof t, "((wl%d >> (k * cur.W[%d])) & lmk%d)", i, i, i);
-      else
-        snprintf(t, sizeof t,
-                 "jit_bread(seg + %uu, cur.bit[%d] + r * cur.W[%d], "
-                 "cur.W[%d])",
-                 off[i], i, i, i);
-      const std::string n = std::to_string(i);
-      const std::string v = "((" + std::string(t) + " ^ cur.lmask[" + n +
-                            "]) + (uint64_t)cur.llo[" + n + "])";
-      std::string e;
-      if (st.leaf_form[i] == OBX_KS_BITMAP)
-        e = "!cur.lnone[" + n + "] &&\n              obx_ks_bit_test(cur.kw[" +
-            n + "], " + v + ",\n              (uint64_t)cur.lhi[" + n + "])";
-      else if (st.leaf_form[i] == OBX_KS_HASH)
-        e = "!cur.lnone[" + n + "] &&\n              obx_ks_hash_test(cur.kw[" +
-            n + "], cur.khi[" + n + "], cur.kshift[" + n + "],\n"
-            "              cur.kmark[" + n + "], " + v + ")";
-      else
-        e = "false"; /* the empty set */
-      return as_bool ? "          const bool lf" + n + " = " + e + ";\n"
-                     : "          if (live)\n            live = " + e + ";\n";
-    };
-    /* sweep of one staged block (emitted inside the block loop below) */
-    std::string sweep;
-    sweep += "      {\n";
-    for (int i = 0; i < NL; i++) {
-      if (st.leaf_kind[i] == 1) {
-        snprintf(b, sizeof b,
-                 "      const bool l%d_all = cur.lall[%d] != 0;\n", i, i);
-        sweep += b;
-      }
-    }
-    const int SR = st.r > 1 ? st.r : 1;
-    if (SR > 1) {
-      /* strip-mined LDS sweep: one packed ds_read covers SR fields,
-         mask assembled via wave-synchronous LDS ORs (as direct mode) */
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(b, sizeof b,
-                   "      const uint64_t lmk%d =\n"
-                   "          ((uint64_t)1 << cur.W[%d]) - 1;\n",
-                   i, i);
-          sweep += b;
-        }
-      sweep +=
-          "      const uint32_t rows = cur.rows;\n"
-          "      const uint64_t row0 = cur.row0;\n"
-          "      const uint32_t tiles = (rows + 64 * FR - 1) / (64 * "
-          "FR);\n"
-          "      for (uint32_t t = wv; t < tiles; t += WAVES) {\n"
-          "        const uint32_t rt = t * 64 * FR + lane * FR;\n"
-          "        if (lane < FR) fm[wv][lane] = 0;\n";
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(b, sizeof b,
-                   "        uint64_t wl%d = (rt < rows)\n"
-                   "            ? jit_bread(seg + %uu, cur.bit[%d] + rt * "
-                   "cur.W[%d], FR * cur.W[%d])\n"
-                   "            : 0;\n",
-                   i, off[i], i, i, i);
-          sweep += b;
-        }
-      sweep += "        uint32_t pm = 0;\n"
-               "#pragma unroll\n"
-               "        for (uint32_t k = 0; k < FR; k++) {\n"
-               "          const uint32_t r = rt + k;\n"
-               "          bool live = r < rows;\n";
-      if (ph.n_prog) {
-        sweep += "          if (live) {\n";
-        for (int i = 0; i < NL; i++) {
-          if (st.leaf_kind[i] == 3) {
-            sweep += set_stmt(i, st.leaf_multi[i] != 0, true);
-            continue;
-          }
-          if (st.leaf_kind[i] == 1) {
-            if (st.leaf_multi[i])
-              snprintf(b, sizeof b,
-                       "          uint64_t v%d = ((wl%d >> (k * cur.W[%d]))"
-                       " & lmk%d) ^ cur.lmask[%d];\n"
-                       "          const bool lf%d = !cur.lnone[%d] &&\n"
-                       "              (l%d_all || (((v%d - cur.llo[%d]) <= "
-                       "(cur.lhi[%d] - cur.llo[%d])) != "
-                       "(bool)cur.linv[%d]));\n",
-                       i, i, i, i, i, i, i, i, i, i, i, i, i);
-            else
-              snprintf(b, sizeof b,
-                       "          uint64_t v%d = jit_bread(seg + %uu, "
-                       "cur.bit[%d] + r * cur.W[%d], cur.W[%d]) ^ "
-                       "cur.lmask[%d];\n"
-                       "          const bool lf%d = !cur.lnone[%d] &&\n"
-                       "              (l%d_all || (((v%d - cur.llo[%d]) <= "
-                       "(cur.lhi[%d] - cur.llo[%d])) != "
-                       "(bool)cur.linv[%d]));\n",
-                       i, off[i], i, i, i, i, i, i, i, i, i, i, i, i);
-          } else {
-            if (st.leaf_multi[i])
-              snprintf(b, sizeof b,
-                       "          const bool lf%d = (cur.lmask[%d] >>\n"
-                       "              (uint32_t)((wl%d >> (k * cur.W[%d])) "
-                       "& lmk%d)) & 1;\n",
-                       i, i, i, i, i);
-            else
-              snprintf(b, sizeof b,
-                       "          const bool lf%d = (cur.lmask[%d] >>\n"
-                       "              (uint32_t)jit_bread(seg + %uu, "
-                       "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                       i, i, off[i], i, i, i);
-          }
-          sweep += b;
-        }
-        sweep += "          live = " + fold_prog("lf%d", true) + ";\n"
-                 "          }\n";
-      } else {
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 3) {
-          sweep += set_stmt(i, st.leaf_multi[i] != 0, false);
-          continue;
-        }
-        if (st.leaf_kind[i] == 1) {
-          if (st.leaf_multi[i])
-            snprintf(b, sizeof b,
-                     "          if (live && !l%d_all) {\n"
-                     "            uint64_t v = ((wl%d >> (k * cur.W[%d])) "
-                     "& lmk%d) ^ cur.lmask[%d];\n"
-                     "            live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                     "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                     "          }\n",
-                     i, i, i, i, i, i, i, i, i);
-          else
-            snprintf(b, sizeof b,
-                     "          if (live && !l%d_all) {\n"
-                     "            uint64_t v = jit_bread(seg + %uu, "
-                     "cur.bit[%d] + r * cur.W[%d], cur.W[%d]) ^ "
-                     "cur.lmask[%d];\n"
-                     "            live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                     "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                     "          }\n",
-                     i, off[i], i, i, i, i, i, i, i, i);
-        } else {
-          if (st.leaf_multi[i])
-            snprintf(b, sizeof b,
-                     "          if (live)\n"
-                     "            live = (cur.lmask[%d] >>\n"
-                     "                    (uint32_t)((wl%d >> (k * "
-                     "cur.W[%d])) & lmk%d)) & 1;\n",
-                     i, i, i, i);
-          else
-            snprintf(b, sizeof b,
-                     "          if (live)\n"
-                     "            live = (cur.lmask[%d] >>\n"
-                     "                    (uint32_t)jit_bread(seg + %uu, "
-                     "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                     i, off[i], i, i, i);
-        }
-        sweep += b;
-      }
-      }
-      snprintf(b, sizeof b,
-               "          pm |= live ? (1u << k) : 0u;\n"
-               "        }\n"
-               "        lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
-               "        if (pm)\n"
-               "          atomicOr(&fm[wv][lane >> %d],\n"
-               "                   (unsigned long long)pm << ((lane & %uu) "
-               "* FR));\n"
-               "#if RID\n"
-               "        if (lane < FR && t * FR + lane < NCH)\n"
-               "          cmask[t * FR + lane] = fm[wv][lane];\n"
-               "#endif\n"
-               "        if (lane < FR) {\n"
-               "          unsigned long long m = fm[wv][lane];\n"
-               "          if (m) {\n"
-               "            const uint64_t pos =\n"
-               "                row0 + (uint64_t)t * (64 * FR) + lane * "
-               "64;\n"
-               "            const uint64_t w0 = pos >> 6;\n"
-               "            const uint32_t sh = (uint32_t)(pos & 63);\n"
-               "            atomicOr(&bitmap[w0], m << sh);\n"
-               "            if (sh && (m >> (64 - sh)))\n"
-               "              atomicOr(&bitmap[w0 + 1], m >> (64 - "
-               "sh));\n"
-               "          }\n"
-               "        }\n"
-               "      }\n"
-               "      }\n",
-               SR == 4 ? 4 : 5, SR == 4 ? 15u : 31u);
-      sweep += b;
-    } else {
-    sweep += "      const uint32_t rows = cur.rows;\n"
-             "      const uint64_t row0 = cur.row0;\n"
-             "      const uint32_t n64 = (rows + 63) >> 6;\n"
-             "      for (uint32_t it = wv; it < n64; it += WAVES) {\n"
-             "        const uint32_t r = it * 64 + lane;\n"
-             "        bool live = r < rows;\n";
-    if (ph.n_prog) {
-      sweep += "        if (live) {\n";
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 3) {
-          sweep += set_stmt(i, false, true);
-          continue;
-        }
-        if (st.leaf_kind[i] == 1)
-          snprintf(b, sizeof b,
-                   "        uint64_t v%d = jit_bread(seg + %uu, cur.bit[%d]"
-                   " + r * cur.W[%d], cur.W[%d]) ^ cur.lmask[%d];\n"
-                   "        const bool lf%d = !cur.lnone[%d] &&\n"
-                   "            (l%d_all || (((v%d - cur.llo[%d]) <= "
-                   "(cur.lhi[%d] - cur.llo[%d])) != "
-                   "(bool)cur.linv[%d]));\n",
-                   i, off[i], i, i, i, i, i, i, i, i, i, i, i, i);
-        else
-          snprintf(b, sizeof b,
-                   "        const bool lf%d = (cur.lmask[%d] >>\n"
-                   "            (uint32_t)jit_bread(seg + %uu, cur.bit[%d] "
-                   "+ r * cur.W[%d], cur.W[%d])) & 1;\n",
-                   i, i, off[i], i, i, i);
-        sweep += b;
-      }
-      sweep += "        live = " + fold_prog("lf%d", true) + ";\n"
-               "        }\n";
-    } else {
-    for (int i = 0; i < NL; i++) {
-      if (st.leaf_kind[i] == 3) {
-        sweep += set_stmt(i, false, false);
-        continue;
-      }
-      if (st.leaf_kind[i] == 1)
-        snprintf(b, sizeof b,
-                 "        if (live && !l%d_all) {\n"
-                 "          uint64_t v = jit_bread(seg + %uu, cur.bit[%d] + "
-                 "r * cur.W[%d], cur.W[%d]) ^ cur.lmask[%d];\n"
-                 "          live = ((v - cur.llo[%d]) <= (cur.lhi[%d] - "
-                 "cur.llo[%d])) != (bool)cur.linv[%d];\n"
-                 "        }\n",
-                 i, off[i], i, i, i, i, i, i, i, i);
-      else
-        snprintf(b, sizeof b,
-                 "        if (live)\n"
-                 "          live = (cur.lmask[%d] >>\n"
-                 "                  (uint32_t)jit_bread(seg + %uu, "
-                 "cur.bit[%d] + r * cur.W[%d], cur.W[%d])) & 1;\n",
-                 i, off[i], i, i, i);
-      sweep += b;
-    }
-    }
-    sweep += "        uint64_t m = __ballot(live);\n"
+               i);
+  }
+  s += "  return true;\n"
+       "}\n"
+       "__device__ __forceinline__ void issue_stage(\n"
+       "    const blkp &p, uint8_t *dst, uint32_t tid) {\n";
+  for (int i = 0; i < NL; i++)
+    jit_emit(s,
+             "  for (uint32_t i2 = tid; i2 * 16 < p.len[%1$d]; i2 += WG)\n"
+             "    __builtin_amdgcn_global_load_lds(\n"
+             "        (const __attribute__((address_space(1))) uint32_t\n"
+             "             *)(p.bp + p.lo[%1$d] + (size_t)i2 * 16),\n"
+             "        (__attribute__((address_space(3))) uint32_t\n"
+             "             *)(dst + %2$uu + (size_t)i2 * 16),\n"
+             "        16, 0, 0);\n",
+             i, jit_f_seg_off(st, i));
+  s += "}\n";
+}
+
+/* staged mode: sweep of one staged block (emitted inside the block loop) */
+static void jit_f_staged_sweep(const dev_plan_hdr &ph,
+                               const jit_fstrategy &st, std::string &s) {
+  const int NL = ph.n_leaves;
+  const int SR = st.r > 1 ? st.r : 1;
+  s += "      {\n";
+  for (int i = 0; i < NL; i++)
+    if (st.leaf_kind[i] == JL_RANGE)
+      jit_emit(s, "      const bool l%1$d_all = cur.lall[%1$d] != 0;\n", i);
+  if (SR > 1) {
+    /* strip-mined LDS sweep: one packed ds_read covers SR fields, mask
+       assembled via wave-synchronous LDS ORs (as direct mode) */
+    for (int i = 0; i < NL; i++)
+      if (st.leaf_multi[i])
+        jit_emit(s,
+                 "      const uint64_t lmk%1$d =\n"
+                 "          ((uint64_t)1 << cur.W[%1$d]) - 1;\n",
+                 i);
+    s += "      const uint32_t rows = cur.rows;\n"
+         "      const uint64_t row0 = cur.row0;\n"
+         "      const uint32_t tiles = (rows + 64 * FR - 1) / (64 * "
+         "FR);\n"
+         "      for (uint32_t t = wv; t < tiles; t += WAVES) {\n"
+         "        const uint32_t rt = t * 64 * FR + lane * FR;\n"
+         "        if (lane < FR) fm[wv][lane] = 0;\n";
+    for (int i = 0; i < NL; i++)
+      if (st.leaf_multi[i])
+        jit_emit(s,
+                 "        uint64_t wl%1$d = (rt < rows)\n"
+                 "            ? jit_bread(seg + %2$uu, cur.bit[%1$d] + rt * "
+                 "cur.W[%1$d], FR * cur.W[%1$d])\n"
+                 "            : 0;\n",
+                 i, jit_f_seg_off(st, i));
+    s += "        uint32_t pm = 0;\n"
+         "#pragma unroll\n"
+         "        for (uint32_t k = 0; k < FR; k++) {\n"
+         "          const uint32_t r = rt + k;\n"
+         "          bool live = r < rows;\n";
+    jit_f_staged_tests(ph, st, 10, true, s);
+    jit_emit(s,
+             "          pm |= live ? (1u << k) : 0u;\n"
+             "        }\n"
+             "        lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
+             "        if (pm)\n"
+             "          atomicOr(&fm[wv][lane >> %d],\n"
+             "                   (unsigned long long)pm << ((lane & %uu) "
+             "* FR));\n"
              "#if RID\n"
-             "        if (lane == 0 && it < NCH) cmask[it] = m;\n"
+             "        if (lane < FR && t * FR + lane < NCH)\n"
+             "          cmask[t * FR + lane] = fm[wv][lane];\n"
              "#endif\n"
-             "        lane_cnt += live ? 1u : 0u;\n"
-             "        if (lane == 0 && m) {\n"
-             "          const uint64_t pos = row0 + (uint64_t)it * 64;\n"
-             "          const uint64_t w0 = pos >> 6;\n"
-             "          const uint32_t sh = (uint32_t)(pos & 63);\n"
-             "          atomicOr(&bitmap[w0], m << sh);\n"
-             "          if (sh && (m >> (64 - sh)))\n"
-             "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
+             "        if (lane < FR) {\n"
+             "          unsigned long long m = fm[wv][lane];\n"
+             "          if (m) {\n"
+             "            const uint64_t pos =\n"
+             "                row0 + (uint64_t)t * (64 * FR) + lane * "
+             "64;\n"
+             "            const uint64_t w0 = pos >> 6;\n"
+             "            const uint32_t sh = (uint32_t)(pos & 63);\n"
+             "            atomicOr(&bitmap[w0], m << sh);\n"
+             "            if (sh && (m >> (64 - sh)))\n"
+             "              atomicOr(&bitmap[w0 + 1], m >> (64 - "
+             "sh));\n"
+             "          }\n"
              "        }\n"
              "      }\n"
-             "      }\n";
-    }
-    if (st.frid) {
-      sweep +=
-          "#if RID\n"
-          "      /* ordered selection vectors from the captured chunk\n"
-          "         masks (get_row_ids shape: block-local int32 row ids\n"
-          "         at the block's absolute row offset) */\n"
-          "      __syncthreads();\n"
-          "      if (tid == 0) {\n"
-          "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
-          "        uint32_t acc = 0;\n"
-          "        for (uint32_t c2 = 0; c2 < n64r; c2++) {\n"
-          "          cpre[c2] = acc;\n"
-          "          acc += (uint32_t)__popcll(cmask[c2]);\n"
-          "        }\n"
-          "        blk_counts[cur.blk] = acc;\n"
-          "      }\n"
-          "      __syncthreads();\n"
-          "      {\n"
-          "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
-          "        for (uint32_t c2 = wv; c2 < n64r; c2 += WAVES) {\n"
-          "          const unsigned long long m2 = cmask[c2];\n"
-          "          if ((m2 >> lane) & 1) {\n"
-          "            const uint32_t pos = cpre[c2] +\n"
-          "                (uint32_t)__popcll(m2 &\n"
-          "                    (((unsigned long long)1 << lane) - 1));\n"
-          "            row_ids[cur.row0 + pos] = (int32_t)(c2 * 64 + "
-          "lane);\n"
-          "          }\n"
-          "        }\n"
-          "      }\n"
-          "#endif\n";
-    }
-    s += "extern \"C\" __global__ __launch_bounds__(256, 8) void "
-         "k_jit_filter(\n"
-         "    const uint8_t *__restrict__ buf, const dev_block "
-         "*__restrict__ blocks,\n"
-         "    uint32_t n_blocks, const dev_leaf *__restrict__ "
-         "plan_leaves,\n"
-         "    const blk_leaf *__restrict__ bleaves,\n"
-         "    unsigned long long *__restrict__ bitmap,\n"
-         "    int32_t *__restrict__ row_ids,\n"
-         "    uint32_t *__restrict__ blk_counts,\n"
-         "    unsigned long long *__restrict__ counters) {\n"
-         "  const uint32_t tid = threadIdx.x;\n"
-         "  const uint32_t lane = tid & 63, wv = tid >> 6;\n"
-         "  uint32_t lane_cnt = 0;\n"
-         "  __shared__ uint8_t seg[SEGSZ];\n"
-         "#if FR > 1\n"
-         "  __shared__ unsigned long long fm[WAVES][FR];\n"
-         "#endif\n"
+             "      }\n",
+             SR == 4 ? 4 : 5, SR == 4 ? 15u : 31u);
+  } else {
+    s += "      const uint32_t rows = cur.rows;\n"
+         "      const uint64_t row0 = cur.row0;\n"
+         "      const uint32_t n64 = (rows + 63) >> 6;\n"
+         "      for (uint32_t it = wv; it < n64; it += WAVES) {\n"
+         "        const uint32_t r = it * 64 + lane;\n"
+         "        bool live = r < rows;\n";
+    jit_f_staged_tests(ph, st, 8, false, s);
+    s += "        uint64_t m = __ballot(live);\n"
          "#if RID\n"
-         "  __shared__ unsigned long long cmask[NCH];\n"
-         "  __shared__ uint32_t cpre[NCH];\n"
+         "        if (lane == 0 && it < NCH) cmask[it] = m;\n"
          "#endif\n"
-         "  __shared__ unsigned long long wsum;\n"
-         "  if (tid == 0) wsum = 0;\n"
-         "  uint32_t bi = blockIdx.x;\n"
-         "  const uint32_t gstep = gridDim.x;\n"
-         "  for (;;) {\n"
-         "    /* next block of this workgroup's stride that any row can pass */\n"
-         "    bool v0 = false;\n"
-         "    blkp cur;\n"
-         "    while (bi < n_blocks) {\n"
-         "      bool ok = load_params(buf, blocks, plan_leaves, "
-         "bleaves, bi, cur);\n"
-         "      bi += gstep;\n"
-         "      if (ok) { v0 = true; break; }\n"
-         "    }\n"
-         "    if (!v0) break;\n"
-         "    __syncthreads(); /* drain previous sweep's LDS reads */\n"
-         "    issue_stage(cur, seg, tid);\n"
-         "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-         "    __syncthreads();\n";
-    s += sweep;
-    s += "  }\n"
-         "  /* one global atomic per WG into a slot striped by blockIdx:\n"
-         "     16k same-address atomics serialized ~0.2 ms at L2 */\n"
-         "  for (int off2 = 32; off2 > 0; off2 >>= 1)\n"
-         "    lane_cnt += (uint32_t)__shfl_xor((int)lane_cnt, off2, 64);\n"
-         "  __syncthreads();\n"
-         "  if (lane == 0 && lane_cnt)\n"
-         "    atomicAdd(&wsum, (unsigned long long)lane_cnt);\n"
-         "  __syncthreads();\n"
-         "  if (tid == 0 && wsum)\n"
-         "    atomicAdd(&counters[8 + (blockIdx.x & 7)], wsum);\n"
-         "}\n";
-    return s;
+         "        lane_cnt += live ? 1u : 0u;\n"
+         "        if (lane == 0 && m) {\n"
+         "          const uint64_t pos = row0 + (uint64_t)it * 64;\n"
+         "          const uint64_t w0 = pos >> 6;\n"
+         "          const uint32_t sh = (uint32_t)(pos & 63);\n"
+         "          atomicOr(&bitmap[w0], m << sh);\n"
+         "          if (sh && (m >> (64 - sh)))\n"
+         "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
+         "        }\n"
+         "      }\n"
+         "      }\n";
   }
+  if (st.frid)
+    s += "#if RID\n"
+         "      /* ordered selection vectors from the captured chunk\n"
+         "         masks (get_row_ids shape: block-local int32 row ids\n"
+         "         at the block's absolute row offset) */\n"
+         "      __syncthreads();\n"
+         "      if (tid == 0) {\n"
+         "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
+         "        uint32_t acc = 0;\n"
+         "        for (uint32_t c2 = 0; c2 < n64r; c2++) {\n"
+         "          cpre[c2] = acc;\n"
+         "          acc += (uint32_t)__popcll(cmask[c2]);\n"
+         "        }\n"
+         "        blk_counts[cur.blk] = acc;\n"
+         "      }\n"
+         "      __syncthreads();\n"
+         "      {\n"
+         "        const uint32_t n64r = (cur.rows + 63) >> 6;\n"
+         "        for (uint32_t c2 = wv; c2 < n64r; c2 += WAVES) {\n"
+         "          const unsigned long long m2 = cmask[c2];\n"
+         "          if ((m2 >> lane) & 1) {\n"
+         "            const uint32_t pos = cpre[c2] +\n"
+         "                (uint32_t)__popcll(m2 &\n"
+         "                    (((unsigned long long)1 << lane) - 1));\n"
+         "            row_ids[cur.row0 + pos] = (int32_t)(c2 * 64 + "
+         "lane);\n"
+         "          }\n"
+         "        }\n"
+         "      }\n"
+         "#endif\n";
+}
+
+/* staged mode: the kernel — workgroup per block, next passing block,
+   stage, sweep; survivor count at the end */
+static void jit_f_staged_kernel(const dev_plan_hdr &ph,
+                                const jit_fstrategy &st, std::string &s) {
+  s += "extern \"C\" __global__ __launch_bounds__(256, 8) void "
+       "k_jit_filter(\n"
+       "    const uint8_t *__restrict__ buf, const dev_block "
+       "*__restrict__ blocks,\n"
+       "    uint32_t n_blocks, const dev_leaf *__restrict__ "
+       "plan_leaves,\n"
+       "    const blk_leaf *__restrict__ bleaves,\n"
+       "    unsigned long long *__restrict__ bitmap,\n"
+       "    int32_t *__restrict__ row_ids,\n"
+       "    uint32_t *__restrict__ blk_counts,\n"
+       "    unsigned long long *__restrict__ counters) {\n"
+       "  const uint32_t tid = threadIdx.x;\n"
+       "  const uint32_t lane = tid & 63, wv = tid >> 6;\n"
+       "  uint32_t lane_cnt = 0;\n"
+       "  __shared__ uint8_t seg[SEGSZ];\n"
+       "#if FR > 1\n"
+       "  __shared__ unsigned long long fm[WAVES][FR];\n"
+       "#endif\n"
+       "#if RID\n"
+       "  __shared__ unsigned long long cmask[NCH];\n"
+       "  __shared__ uint32_t cpre[NCH];\n"
+       "#endif\n"
+       "  __shared__ unsigned long long wsum;\n"
+       "  if (tid == 0) wsum = 0;\n"
+       "  uint32_t bi = blockIdx.x;\n"
+       "  const uint32_t gstep = gridDim.x;\n"
+       "  for (;;) {\n"
+       "    /* next block of this workgroup's stride that any row can pass */\n"
+       "    bool v0 = false;\n"
+       "    blkp cur;\n"
+       "    while (bi < n_blocks) {\n"
+       "      bool ok = load_params(buf, blocks, plan_leaves, "
+       "bleaves, bi, cur);\n"
+       "      bi += gstep;\n"
+       "      if (ok) { v0 = true; break; }\n"
+       "    }\n"
+       "    if (!v0) break;\n"
+       "    __syncthreads(); /* drain previous sweep's LDS reads */\n"
+       "    issue_stage(cur, seg, tid);\n"
+       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+       "    __syncthreads();\n";
+  jit_f_staged_sweep(ph, st, s);
+  s += "  }\n"
+       "  /* one global atomic per WG into a slot striped by blockIdx:\n"
+       "     16k same-address atomics serialized ~0.2 ms at L2 */\n"
+       "  for (int off2 = 32; off2 > 0; off2 >>= 1)\n"
+       "    lane_cnt += (uint32_t)__shfl_xor((int)lane_cnt, off2, 64);\n"
+       "  __syncthreads();\n"
+       "  if (lane == 0 && lane_cnt)\n"
+       "    atomicAdd(&wsum, (unsigned long long)lane_cnt);\n"
+       "  __syncthreads();\n"
+       "  if (tid == 0 && wsum)\n"
+       "    atomicAdd(&counters[8 + (blockIdx.x & 7)], wsum);\n"
+       "}\n";
+}
+
+/* direct mode, strip-mined: a tile is 64*FR rows per wave. The packed
+   loads of tile `itx`, into names suffixed sfx ... */
+static void jit_f_direct_loads(const dev_plan_hdr &ph,
+                               const jit_fstrategy &st, const char *sfx,
+                               const char *itx, std::string &s) {
+  jit_emit(s,
+           "      const uint32_t rt%s = rbeg + (%s) * 64 * FR + lane * "
+           "FR;\n",
+           sfx, itx);
+  for (int i = 0; i < (int)ph.n_leaves; i++)
+    if (st.leaf_multi[i])
+      jit_emit(s,
+               "      uint64_t wl%1$d%2$s = (rt%2$s < rend)\n"
+               "          ? jit_bread(bp, l%1$do + rt%2$s * l%1$dW, FR * "
+               "l%1$dW)\n"
+               "          : 0;\n",
+               i, sfx);
+}
+
+/* ... and the tile body that consumes them */
+static void jit_f_direct_tile(const dev_plan_hdr &ph,
+                              const jit_fstrategy &st, const char *sfx,
+                              const char *itx, std::string &s) {
+  s += "      if (lane < FR) fm[wv][lane] = 0;\n"
+       "      {\n"
+       "      uint32_t pm = 0;\n"
+       "#pragma unroll\n"
+       "      for (uint32_t k = 0; k < FR; k++) {\n";
+  jit_emit(s,
+           "        const uint32_t r = rt%s + k;\n"
+           "        bool live = r < rend;\n",
+           sfx);
+  jit_f_direct_tests(ph, st, 8, sfx, true, s);
+  jit_emit(s,
+           "        pm |= live ? (1u << k) : 0u;\n"
+           "      }\n"
+           "      lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
+           "      /* wave-synchronous LDS mask assembly: DS ops of one\n"
+           "         wave execute in program order (lockstep wave64), "
+           "so\n"
+           "         the read below sees every lane's OR, barrier-free "
+           "*/\n"
+           "      if (pm)\n"
+           "        atomicOr(&fm[wv][lane >> %d],\n"
+           "                 (unsigned long long)pm << ((lane & %uu) * "
+           "FR));\n"
+           "      if (lane < FR) {\n"
+           "        unsigned long long m = fm[wv][lane];\n"
+           "        if (m) {\n"
+           "          const uint64_t pos =\n"
+           "              row0 + (uint64_t)(%s) * (64 * FR) + lane * "
+           "64;\n"
+           "          const uint64_t w0 = pos >> 6;\n"
+           "          const uint32_t sh = (uint32_t)(pos & 63);\n"
+           "          atomicOr(&bitmap[w0], m << sh);\n"
+           "          if (sh && (m >> (64 - sh)))\n"
+           "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
+           "        }\n"
+           "      }\n"
+           "      }\n",
+           st.r == 4 ? 4 : 5, st.r == 4 ? 15u : 31u, itx);
+}
+
+/* direct mode: the kernel — wave per block slice, no barriers */
+static void jit_f_direct_kernel(const dev_plan_hdr &ph,
+                                const jit_fstrategy &st, std::string &s) {
+  const int NL = ph.n_leaves;
   s += "extern \"C\" __global__ __launch_bounds__(256, 8) void "
        "k_jit_filter(\n"
        "    const uint8_t *__restrict__ buf, const dev_block *__restrict__ "
@@ -698,200 +679,63 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
        "        (rbeg + chunk < all_rows) ? rbeg + chunk : all_rows;\n"
        "    const uint64_t row0 = dev_block_row_start(&cur) + rbeg;\n";
   for (int i = 0; i < NL; i++) {
-    snprintf(b, sizeof b,
-             "    const blk_leaf lb%d = bl[%d];\n"
-             "    const uint32_t l%do =\n"
-             "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
-             "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
-             i, i, i, (unsigned)st.leaf_cols[i], i,
-             (unsigned)st.leaf_cols[i]);
-    s += b;
-    if (st.leaf_kind[i] == 1) {
-      snprintf(b, sizeof b,
-               "    const bool l%d_all = lb%d.mode == OBX_LEAF_ALL;\n", i, i);
-      s += b;
-    }
+    jit_emit(s,
+             "    const blk_leaf lb%1$d = bl[%1$d];\n"
+             "    const uint32_t l%1$do =\n"
+             "        (uint32_t)(cur.cols[%2$u].data_bit - blk_bit);\n"
+             "    const uint32_t l%1$dW = PW(cur.cols[%2$u]);\n",
+             i, (unsigned)st.leaf_cols[i]);
+    if (st.leaf_kind[i] == JL_RANGE)
+      jit_emit(s,
+               "    const bool l%1$d_all = lb%1$d.mode == OBX_LEAF_ALL;\n", i);
   }
-  const int R = st.r > 1 ? st.r : 1;
-  if (R > 1) {
+  if (st.r > 1) {
     for (int i = 0; i < NL; i++)
-      if (st.leaf_multi[i]) {
-        snprintf(b, sizeof b,
-                 "    const uint64_t lmk%d = ((uint64_t)1 << l%dW) - 1;\n",
-                 i, i);
-        s += b;
-      }
+      if (st.leaf_multi[i])
+        jit_emit(s,
+                 "    const uint64_t lmk%1$d = ((uint64_t)1 << l%1$dW) - 1;\n",
+                 i);
+    /* the superiteration emits FU tiles' loads before any tile body, so
+       each wave keeps FU independent HBM fetches in flight (in-order vmcnt
+       retirement pipelines them) */
     const int FU = st.fu > 0 ? st.fu : 1;
-    /* tile = 64*FR rows per wave; `emit_pre` issues the tile's packed
-       loads, `emit_tile` consumes them — the superiteration emits FU
-       pre-blocks before any tile body so each wave keeps FU independent
-       HBM fetches in flight (in-order vmcnt retirement pipelines them) */
-    auto emit_pre = [&](const std::string &sfx, const std::string &itx) {
-      std::string o;
-      char bb[512];
-      snprintf(bb, sizeof bb,
-               "      const uint32_t rt%s = rbeg + (%s) * 64 * FR + lane * "
-               "FR;\n",
-               sfx.c_str(), itx.c_str());
-      o += bb;
-      for (int i = 0; i < NL; i++)
-        if (st.leaf_multi[i]) {
-          snprintf(bb, sizeof bb,
-                   "      uint64_t wl%d%s = (rt%s < rend)\n"
-                   "          ? jit_bread(bp, l%do + rt%s * l%dW, FR * "
-                   "l%dW)\n"
-                   "          : 0;\n",
-                   i, sfx.c_str(), sfx.c_str(), i, sfx.c_str(), i, i);
-          o += bb;
-        }
-      return o;
-    };
-    auto emit_tile = [&](const std::string &sfx, const std::string &itx) {
-      std::string o;
-      char bb[1024];
-      o += "      if (lane < FR) fm[wv][lane] = 0;\n"
-           "      {\n"
-           "      uint32_t pm = 0;\n"
-           "#pragma unroll\n"
-           "      for (uint32_t k = 0; k < FR; k++) {\n";
-      snprintf(bb, sizeof bb,
-               "        const uint32_t r = rt%s + k;\n"
-               "        bool live = r < rend;\n",
-               sfx.c_str());
-      o += bb;
-      for (int i = 0; i < NL; i++) {
-        if (st.leaf_kind[i] == 1) {
-          if (st.leaf_multi[i])
-            snprintf(bb, sizeof bb,
-                     "        if (live && !l%d_all) {\n"
-                     "          uint64_t v = ((wl%d%s >> (k * l%dW)) & "
-                     "lmk%d) ^ lb%d.mask;\n"
-                     "          live = ((v - lb%d.lo) <= (lb%d.hi - "
-                     "lb%d.lo)) != (bool)lb%d.invert;\n"
-                     "        }\n",
-                     i, i, sfx.c_str(), i, i, i, i, i, i, i);
-          else
-            snprintf(bb, sizeof bb,
-                     "        if (live && !l%d_all) {\n"
-                     "          uint64_t v = jit_bread(bp, l%do + r * "
-                     "l%dW, l%dW) ^ lb%d.mask;\n"
-                     "          live = ((v - lb%d.lo) <= (lb%d.hi - "
-                     "lb%d.lo)) != (bool)lb%d.invert;\n"
-                     "        }\n",
-                     i, i, i, i, i, i, i, i, i);
-        } else {
-          if (st.leaf_multi[i])
-            snprintf(bb, sizeof bb,
-                     "        if (live)\n"
-                     "          live = (lb%d.mask >>\n"
-                     "                  (uint32_t)((wl%d%s >> (k * l%dW)) "
-                     "& lmk%d)) & 1;\n",
-                     i, i, sfx.c_str(), i, i);
-          else
-            snprintf(bb, sizeof bb,
-                     "        if (live)\n"
-                     "          live = (lb%d.mask >>\n"
-                     "                  (uint32_t)jit_bread(bp, l%do + r "
-                     "* l%dW, l%dW)) & 1;\n",
-                     i, i, i, i);
-        }
-        o += bb;
-      }
-      snprintf(bb, sizeof bb,
-               "        pm |= live ? (1u << k) : 0u;\n"
-               "      }\n"
-               "      lane_cnt += (uint32_t)__builtin_popcount(pm);\n"
-               "      /* wave-synchronous LDS mask assembly: DS ops of one\n"
-               "         wave execute in program order (lockstep wave64), "
-               "so\n"
-               "         the read below sees every lane's OR, barrier-free "
-               "*/\n"
-               "      if (pm)\n"
-               "        atomicOr(&fm[wv][lane >> %d],\n"
-               "                 (unsigned long long)pm << ((lane & %uu) * "
-               "FR));\n"
-               "      if (lane < FR) {\n"
-               "        unsigned long long m = fm[wv][lane];\n"
-               "        if (m) {\n"
-               "          const uint64_t pos =\n"
-               "              row0 + (uint64_t)(%s) * (64 * FR) + lane * "
-               "64;\n"
-               "          const uint64_t w0 = pos >> 6;\n"
-               "          const uint32_t sh = (uint32_t)(pos & 63);\n"
-               "          atomicOr(&bitmap[w0], m << sh);\n"
-               "          if (sh && (m >> (64 - sh)))\n"
-               "            atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
-               "        }\n"
-               "      }\n"
-               "      }\n",
-               R == 4 ? 4 : 5, R == 4 ? 15u : 31u, itx.c_str());
-      o += bb;
-      return o;
-    };
     s += "    const uint32_t nr = rend - rbeg;\n"
          "    const uint32_t iters = (nr + 64 * FR - 1) / (64 * FR);\n"
          "    uint32_t it = 0;\n";
     if (FU > 1) {
-      snprintf(b, sizeof b, "    for (; it + %d <= iters; it += %d) {\n",
-               FU, FU);
-      s += b;
-      for (int u = 0; u < FU; u++) {
-        char sfx[8], itx[16];
-        snprintf(sfx, sizeof sfx, "_%d", u);
-        snprintf(itx, sizeof itx, "it + %d", u);
-        s += emit_pre(sfx, itx);
-      }
-      for (int u = 0; u < FU; u++) {
-        char sfx[8], itx[16];
-        snprintf(sfx, sizeof sfx, "_%d", u);
-        snprintf(itx, sizeof itx, "it + %d", u);
-        s += emit_tile(sfx, itx);
-      }
+      jit_emit(s, "    for (; it + %1$d <= iters; it += %1$d) {\n", FU);
+      for (int u = 0; u < FU; u++)
+        jit_f_direct_loads(ph, st, jit_fmt("_%d", u).c_str(),
+                           jit_fmt("it + %d", u).c_str(), s);
+      for (int u = 0; u < FU; u++)
+        jit_f_direct_tile(ph, st, jit_fmt("_%d", u).c_str(),
+                          jit_fmt("it + %d", u).c_str(), s);
       s += "    }\n";
     }
     s += "    for (; it < iters; it++) {\n";
-    s += emit_pre("", "it");
-    s += emit_tile("", "it");
+    jit_f_direct_loads(ph, st, "", "it", s);
+    jit_f_direct_tile(ph, st, "", "it", s);
     s += "    }\n"
          "  }\n";
   } else {
-  s += "    const uint32_t nr = rend - rbeg;\n"
-       "    const uint32_t iters = (nr + 63) / 64;\n"
-       "    for (uint32_t it = 0; it < iters; it++) {\n"
-       "      const uint32_t r = rbeg + it * 64 + lane;\n"
-       "      bool live = r < rend;\n";
-  for (int i = 0; i < NL; i++) {
-    if (st.leaf_kind[i] == 1) {
-      snprintf(b, sizeof b,
-               "      if (live && !l%d_all) {\n"
-               "        uint64_t v = jit_bread(bp, l%do + r * l%dW, l%dW) ^ "
-               "lb%d.mask;\n"
-               "        live = ((v - lb%d.lo) <= (lb%d.hi - lb%d.lo)) != "
-               "(bool)lb%d.invert;\n"
-               "      }\n",
-               i, i, i, i, i, i, i, i, i);
-    } else {
-      snprintf(b, sizeof b,
-               "      if (live)\n"
-               "        live = (lb%d.mask >>\n"
-               "                (uint32_t)jit_bread(bp, l%do + r * l%dW, "
-               "l%dW)) & 1;\n",
-               i, i, i, i);
-    }
-    s += b;
-  }
-  s += "      uint64_t m = __ballot(live);\n"
-       "      lane_cnt += live ? 1u : 0u;\n"
-       "      if (lane == 0 && m) {\n"
-       "        const uint64_t pos = row0 + (uint64_t)it * 64;\n"
-       "        const uint64_t w0 = pos >> 6;\n"
-       "        const uint32_t sh = (uint32_t)(pos & 63);\n"
-       "        atomicOr(&bitmap[w0], m << sh);\n"
-       "        if (sh && (m >> (64 - sh)))\n"
-       "          atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
-       "      }\n"
-       "    }\n"
-       "  }\n";
+    s += "    const uint32_t nr = rend - rbeg;\n"
+         "    const uint32_t iters = (nr + 63) / 64;\n"
+         "    for (uint32_t it = 0; it < iters; it++) {\n"
+         "      const uint32_t r = rbeg + it * 64 + lane;\n"
+         "      bool live = r < rend;\n";
+    jit_f_direct_tests(ph, st, 6, "", false, s);
+    s += "      uint64_t m = __ballot(live);\n"
+         "      lane_cnt += live ? 1u : 0u;\n"
+         "      if (lane == 0 && m) {\n"
+         "        const uint64_t pos = row0 + (uint64_t)it * 64;\n"
+         "        const uint64_t w0 = pos >> 6;\n"
+         "        const uint32_t sh = (uint32_t)(pos & 63);\n"
+         "        atomicOr(&bitmap[w0], m << sh);\n"
+         "        if (sh && (m >> (64 - sh)))\n"
+         "          atomicOr(&bitmap[w0 + 1], m >> (64 - sh));\n"
+         "      }\n"
+         "    }\n"
+         "  }\n";
   }
   s += "  for (int off = 32; off > 0; off >>= 1)\n"
        "    lane_cnt += (uint32_t)__shfl_xor((int)lane_cnt, off, 64);\n"
@@ -902,5 +746,18 @@ static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
        "  if (tid == 0 && wsum)\n"
        "    atomicAdd(&counters[8 + (blockIdx.x & 7)], wsum);\n"
        "}\n";
+}
+
+static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
+                                         const jit_fstrategy &st) {
+  std::string s;
+  jit_f_prologue(ph, st, s);
+  if (st.fstage) {
+    jit_f_staged_params(ph, st, s);
+    jit_f_staged_kernel(ph, st, s); /* holds jit_f_staged_sweep */
+  } else {
+    jit_f_direct_kernel(ph, st, s);
+  }
   return s;
 }
+

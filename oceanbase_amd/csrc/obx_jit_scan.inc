@@ -69,6 +69,12 @@
  *
  * Anything outside these bounds falls back to the v1 generator (exact
  * digit-split path) or the precompiled kernels. OBX_JIT_V2=0 forces v1.
+ *
+ * Layout: jit_build_strategy (the only place that reads the environment;
+ * knob -> field list in obx_jit.inc), jit_strategy_sig, the fragments the
+ * phases share (packed read, mask, field, product operand, one copy each),
+ * then one function per kernel phase; jit_gen_source_v2 at the end lists
+ * them in kernel order.
  */
 
 enum { JV_CTX = 0, JV_REF = 1 };
@@ -83,10 +89,18 @@ enum {
 };
 
 struct jit_vtab {          /* per-block LDS value table over dict refs */
-  uint8_t vc;              /* value-col slot (js.vcol index) */
-  uint8_t kind;            /* 0 ident, 1 (one - e), 2 (one + e) */
-  int64_t one;
-  uint32_t dim;            /* maxcnt + 1 */
+  uint8_t vc = 0;          /* value-col slot (js.vcol index) */
+  uint8_t kind = 0;        /* 0 ident, 1 (one - e), 2 (one + e) */
+  int64_t one = 0;
+  uint32_t dim = 0;        /* maxcnt + 1 */
+};
+
+/* per-aggregate slot ids of a strategy: -1 = none */
+struct jit_agg_ids {
+  int8_t v[OBX_DEV_MAX_AGGS];
+  jit_agg_ids() { for (int8_t &x : v) x = -1; }
+  int8_t &operator[](size_t a) { return v[a]; }
+  const int8_t &operator[](size_t a) const { return v[a]; }
 };
 
 struct jit_strategy {
@@ -96,14 +110,14 @@ struct jit_strategy {
   uint8_t vraw8[4] = {};     /* CTX col is aligned 8-B RAW in every block */
   uint32_t vdim[4] = {};     /* REF: maxcnt+1 */
   uint8_t astrat[OBX_DEV_MAX_AGGS] = {};
-  int8_t wa64[OBX_DEV_MAX_AGGS];    /* JA_I64*: wacc64 slot */
-  int8_t amm[OBX_DEV_MAX_AGGS];     /* JA_MM: wmm slot */
+  jit_agg_ids wa64;    /* JA_I64*: wacc64 slot */
+  jit_agg_ids amm;     /* JA_MM: wmm slot */
   int n_mm = 0;
-  int8_t ahist[OBX_DEV_MAX_AGGS];   /* JA_HIST/HCOUNT: hist id */
-  int8_t atab_b[OBX_DEV_MAX_AGGS];  /* product b operand: table id or -1 */
-  int8_t atab_c[OBX_DEV_MAX_AGGS];  /* product c operand: table id or -1 */
-  int8_t aval_a[OBX_DEV_MAX_AGGS];  /* a operand: value-col slot or -1 */
-  int8_t atab_a[OBX_DEV_MAX_AGGS];  /* a operand via ident table: id or -1 */
+  jit_agg_ids ahist;   /* JA_HIST/HCOUNT: hist id */
+  jit_agg_ids atab_b;  /* product b operand: table id or -1 */
+  jit_agg_ids atab_c;  /* product c operand: table id or -1 */
+  jit_agg_ids aval_a;  /* a operand: value-col slot or -1 */
+  jit_agg_ids atab_a;  /* a operand via ident table: id or -1 */
   int n_w64 = 0;
   int n_hist = 0;
   uint8_t hist_vc[4] = {};   /* hist id -> value-col slot */
@@ -111,9 +125,9 @@ struct jit_strategy {
   uint32_t hist_off[4] = {}; /* u32 offsets into the shared hist array */
   uint32_t hist_total = 0;   /* total u32 slots */
   int n_tab = 0;
-  jit_vtab tabs[6];
+  jit_vtab tabs[6] = {};
   uint8_t leaf_inline = 0;   /* ALL leaves inline-evaluable in the sweep */
-  uint8_t leaf_kind[8] = {}; /* 1 = packed range, 2 = dict ref mask */
+  uint8_t leaf_kind[8] = {}; /* JL_RANGE or JL_MASK */
   uint16_t leaf_cols[8] = {};
   uint8_t r = 1;             /* rows per lane (strip mining) */
   uint8_t stripes = 4;       /* i64 accumulator lane stripes */
@@ -140,8 +154,8 @@ struct jit_strategy {
   uint32_t jws_d0 = 1, jws_d1 = 1;          /* axis dims */
   uint32_t jws_cells = 16;                  /* group-cell rows */
   uint8_t jws_member[OBX_DEV_MAX_AGGS] = {};
-  int8_t jws_f0[OBX_DEV_MAX_AGGS];          /* flush factor tab / axis0 */
-  int8_t jws_f1[OBX_DEV_MAX_AGGS];          /* flush factor tab / axis1 */
+  jit_agg_ids jws_f0;                       /* flush factor tab / axis0 */
+  jit_agg_ids jws_f1;                       /* flush factor tab / axis1 */
   /* narrowed PROD3: when the weight is a CTX column proven in [0, 2^32)
      and both dict factors are proven non-negative with a product below
      2^32, the per-row term is ONE u32 x u32 -> u64 multiply against a
@@ -222,14 +236,10 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   if (pl && ph.n_leaves >= 1 && ph.n_leaves <= 4) {
     st.leaf_inline = 1;
     for (uint32_t i = 0; i < ph.n_leaves; i++) {
-      uint16_t col = pl[i].col;
-      /* multi-column black programs cannot lower to a ref mask */
-      bool mask_ok = pl[i].op != 10 || pl[i].n_bcols == 1;
-      if (h.col_dict_any[col] && mask_ok) st.leaf_kind[i] = 2;
-      else if (pl[i].op <= 6 && h.col_rangefam_every[col])
-        st.leaf_kind[i] = 1;
-      else { st.leaf_inline = 0; break; }
-      st.leaf_cols[i] = col;
+      const uint8_t kind = jit_leaf_kind(h, pl[i]);
+      if (kind != JL_RANGE && kind != JL_MASK) { st.leaf_inline = 0; break; }
+      st.leaf_kind[i] = kind;
+      st.leaf_cols[i] = pl[i].col;
     }
     if (!st.leaf_inline)
       for (uint32_t i = 0; i < 8; i++) st.leaf_kind[i] = 0;
@@ -268,13 +278,6 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   /* persistent group cells need stable group dicts */
   for (uint32_t g2 = 0; g2 < ph.n_group_cols; g2++)
     if (!h.col_dict_stable[ph.need_cols[ph.group_idx[g2]]]) return false;
-  auto slot_of = [&](uint8_t need_idx) -> int {
-    if (need_idx == 0xFF) return -1;
-    uint16_t col = ph.need_cols[need_idx];
-    for (int j = 0; j < js.n_vc; j++)
-      if (js.vcol[j] == col) return j;
-    return -1;
-  };
   auto maxabs_of = [&](uint8_t need_idx, uint64_t *out) -> bool {
     if (need_idx == 0xFF) return false;
     return jit_col_maxabs(h, ph.need_cols[need_idx], out);
@@ -283,10 +286,8 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   /* choose per-aggregate strategies (everything must fit or v2 is off) */
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     const dev_agg &g = ph.aggs[a];
-    st.wa64[a] = st.ahist[a] = st.atab_b[a] = st.atab_c[a] = -1;
-    st.aval_a[a] = st.atab_a[a] = -1;
-    st.amm[a] = -1;
-    int ja = slot_of(g.ia), jb = slot_of(g.ib), jc = slot_of(g.ic);
+    const int ja = js.slot(ph, g.ia), jb = js.slot(ph, g.ib),
+              jc = js.slot(ph, g.ic);
     uint64_t ma = 0, mb = 0, mc = 0;
     switch (g.kind) {
       case OBX_AGG_COUNT:
@@ -403,8 +404,6 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   /* weighted joint histogram detection: members are JA_I64 aggregates
      whose weight operand is the same CTX column and whose other operands
      are dict-REF columns spanning at most two axes */
-  for (uint32_t a = 0; a < OBX_DEV_MAX_AGGS; a++)
-    st.jws_f0[a] = st.jws_f1[a] = -1;
   {
     const char *je = getenv("OBX_JIT_JWS");
     bool allow = !je || je[0] != '0';
@@ -682,154 +681,145 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   return true;
 }
 
-static std::string jit_strategy_sig(const jit_strategy &st) {
-  char b[256];
+/* every strategy field the generated text reads; per-aggregate entries
+   only for the plan's aggregates (the plan signature in front fixes their
+   number, so the key stays injective) */
+static std::string jit_strategy_sig(const dev_plan_hdr &ph,
+                                    const jit_strategy &st) {
   std::string k = "V2|";
-  snprintf(b, sizeof b, "w%dh%dt%dp%dli%dr%dch%ds%du%uc%um%d|",
-           st.n_w64, st.n_hist, st.n_tab, st.wpb, st.leaf_inline, st.r,
-           st.cnt_hist, st.stripes, st.stage_bytes, st.jcells, st.n_mm);
-  k += b;
-  for (int i = 0; i < 8; i++) {
-    snprintf(b, sizeof b, "m%d%d%d|",
-             i < 8 ? st.leaf_multi[i] + 2 * st.leaf_m32[i] : 0,
+  jit_emit(k, "w%dh%dt%dp%dli%dr%dch%ds%du%uc%um%d|", st.n_w64, st.n_hist,
+           st.n_tab, st.wpb, st.leaf_inline, st.r, st.cnt_hist, st.stripes,
+           st.stage_bytes, st.jcells, st.n_mm);
+  for (int i = 0; i < 8; i++)
+    jit_emit(k, "m%d%d%d|", st.leaf_multi[i] + 2 * st.leaf_m32[i],
              i < 2 ? st.g_multi[i] + 2 * st.g_m32[i] : 0,
              i < 4 ? st.v_multi[i] + 2 * st.v_m32[i] : 0);
-    k += b;
-  }
-  for (int i = 0; i < 8; i++) {
-    snprintf(b, sizeof b, "L%d:%u|", st.leaf_kind[i], st.leaf_cols[i]);
-    k += b;
-  }
-  for (int j = 0; j < 4; j++) {
-    snprintf(b, sizeof b, "v%d:%u:%u:%u|", st.vmode[j], st.vdim[j],
-             st.vext[j], st.vraw8[j]);
-    k += b;
-  }
-  for (int a = 0; a < OBX_DEV_MAX_AGGS; a++) {
-    snprintf(b, sizeof b, "a%d:%d:%d:%d:%d:%d:%d|", st.astrat[a],
-             st.wa64[a], st.ahist[a], st.atab_b[a], st.atab_c[a],
-             st.atab_a[a], st.amm[a]);
-    k += b;
-  }
-  for (int t = 0; t < st.n_tab; t++) {
-    snprintf(b, sizeof b, "T%u:%u:%lld:%u|", st.tabs[t].vc, st.tabs[t].kind,
+  for (int i = 0; i < 8; i++)
+    jit_emit(k, "L%d:%u|", st.leaf_kind[i], st.leaf_cols[i]);
+  for (int j = 0; j < 4; j++)
+    jit_emit(k, "v%d:%u:%u:%u|", st.vmode[j], st.vdim[j], st.vext[j],
+             st.vraw8[j]);
+  for (uint32_t a = 0; a < ph.n_aggs; a++)
+    jit_emit(k, "a%d:%d:%d:%d:%d:%d:%d:%d|", st.astrat[a], st.wa64[a],
+             st.ahist[a], st.atab_b[a], st.atab_c[a], st.atab_a[a],
+             st.amm[a], st.aval_a[a]);
+  for (int t = 0; t < st.n_tab; t++)
+    jit_emit(k, "T%u:%u:%lld:%u|", st.tabs[t].vc, st.tabs[t].kind,
              (long long)st.tabs[t].one, st.tabs[t].dim);
-    k += b;
-  }
-  snprintf(b, sizeof b, "C%d:%u:%u|", st.ctab_agg, st.ctab_db, st.ctab_dc);
-  k += b;
-  snprintf(b, sizeof b, "B%d", st.bdesc);
-  k += b;
-  for (uint32_t i = 0; i < st.bd_cols.n; i++) {
-    snprintf(b, sizeof b, ":%u", st.bd_cols.c[i]);
-    k += b;
-  }
+  for (int t = 0; t < st.n_hist; t++)
+    jit_emit(k, "H%u:%d:%u|", st.hist_vc[t], st.hist_tab[t], st.hist_off[t]);
+  jit_emit(k, "C%d:%u:%u|", st.ctab_agg, st.ctab_db, st.ctab_dc);
+  jit_emit(k, "B%d", st.bdesc);
+  for (uint32_t i = 0; i < st.bd_cols.n; i++)
+    jit_emit(k, ":%u", st.bd_cols.c[i]);
   k += "|";
   if (st.jws_on) {
-    snprintf(b, sizeof b, "J%d:%d:%d:%u:%u:%u|", st.jws_ja, st.jws_a0,
-             st.jws_a1, st.jws_d0, st.jws_d1, st.jws_cells);
-    k += b;
-    for (uint32_t a = 0; a < OBX_DEV_MAX_AGGS; a++) {
-      snprintf(b, sizeof b, "j%d:%d:%d|", st.jws_member[a], st.jws_f0[a],
+    jit_emit(k, "J%d:%d:%d:%u:%u:%u|", st.jws_ja, st.jws_a0, st.jws_a1,
+             st.jws_d0, st.jws_d1, st.jws_cells);
+    for (uint32_t a = 0; a < ph.n_aggs; a++)
+      jit_emit(k, "j%d:%d:%d|", st.jws_member[a], st.jws_f0[a],
                st.jws_f1[a]);
-      k += b;
-    }
   }
   return k;
 }
 
-/* Block-loop head of the persistent scan when the strategy reads the packed
-   descriptor (st.bdesc): verdict, stage and per-block geometry come from a
-   jmeta in registers, never from blocks[blk] -- except a CTX value column
-   that needs a full col_ctx (not raw8), which reads its dev_col as before.
-   The jmeta is loaded at the top of the iteration: scalar loads from two
-   cache lines (leaf tests, record), then the stage DMA, where dev_block
-   cost four dependent round trips over up to six lines. Loading it one
-   block ahead, behind the stage DMA, measured slower and is not carried
-   (profiles/r05_scan_bdesc.md). */
-static void jit_gen_block_head_bdesc(const dev_plan_hdr &ph,
-                                     const jit_shape &js,
-                                     const jit_strategy &st, std::string &s) {
-  const int NG = ph.n_group_cols;
-  const int NL = ph.n_leaves;
-  char b[1024];
-  s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
-       "gridDim.x) {\n"
-       "    jmeta cm;\n"
-       "    jit_load_meta(cm, bdesc, bleaves, blk);\n"
-       "    uint8_t blk_verdict = 1;\n";
-  for (int i = 0; i < NL; i++) {
-    snprintf(b, sizeof b,
-             "    {\n"
-             "      const uint8_t c = jit_leaf_class(\n"
-             "          cm.lf[%d], OBX_BD_FLAGS(cm.s[%d]));\n"
-             "      if (c == 0) blk_verdict = 0;\n"
-             "      else if (c == 2 && blk_verdict) blk_verdict = 2;\n"
-             "    }\n",
-             i, jit_bd_slot(st, st.leaf_cols[i]));
-    s += b;
-  }
-  s += "    if (blk_verdict == 0) continue;\n"
-       "    __syncthreads(); /* drain previous block's LDS reads */\n"
-       "    stage2(buf, cm.byte, cm.len, lds_blk);\n"
-       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-       "    __syncthreads();\n"
-       "    const uint64_t blk_bit = cm.byte * 8;\n"
-       "    blk_view bv;\n"
-       "    bv.base = lds_blk;\n"
-       "    bv.bit_bias = blk_bit;\n"
-       "    bv.rbase_bit = 0;\n"
-       "    const uint32_t rows = cm.rows;\n"
-       "\n";
-  for (int g = 0; g < NG && g < 2; g++) {
-    const int k = jit_bd_slot(st, ph.need_cols[ph.group_idx[g]]);
-    snprintf(b, sizeof b,
-             "    const uint32_t go%d = OBX_BD_OFF(cm.s[%d]);\n"
-             "    const uint32_t gW%d = OBX_BD_WIDTH(cm.s[%d]);\n"
-             "    const uint32_t gn%d = OBX_BD_COUNT(cm.s[%d]);\n",
-             g, k, g, k, g, k);
-    s += b;
-  }
-  if (NG > 1) s += "    const uint32_t dim0 = gn0 + 1;\n";
-  for (int j = 0; j < js.n_vc; j++) {
-    const int k = jit_bd_slot(st, js.vcol[j]);
-    if (st.vmode[j] == JV_REF)
-      snprintf(b, sizeof b,
-               "    const uint32_t xo%d = OBX_BD_OFF(cm.s[%d]);\n"
-               "    const uint32_t xW%d = OBX_BD_WIDTH(cm.s[%d]);\n"
-               "    const uint32_t xn%d = OBX_BD_COUNT(cm.s[%d]);\n",
-               j, k, j, k, j, k);
-    else if (st.vraw8[j])
-      snprintf(b, sizeof b,
-               "    const uint32_t vb%d = OBX_BD_OFF(cm.s[%d]) >> 3;\n", j, k);
-    else
-      snprintf(b, sizeof b,
-               "    const col_ctx c%d =\n"
-               "        make_col_ctx(blocks[blk].cols[%u], blk_bit);\n",
-               j, (unsigned)js.vcol[j]);
-    s += b;
-  }
+/* ---- fragments the phases share ---- */
+
+/* the three kinds of packed stream the sweep reads */
+static jit_stream jit_v2_leaf_stream(int i) {
+  return {jit_fmt("wl%d", i), jit_fmt("l%dW", i), jit_fmt("lm%d", i),
+          "bv.base", jit_fmt("l%do", i)};
+}
+static jit_stream jit_v2_group_stream(int g) {
+  return {jit_fmt("wgr%d", g), jit_fmt("gW%d", g), jit_fmt("gm%d", g),
+          "bv.base", jit_fmt("go%d", g)};
+}
+static jit_stream jit_v2_value_stream(int j) {
+  return {jit_fmt("wx%d", j), jit_fmt("xW%d", j), jit_fmt("xm%d", j),
+          "bv.base", jit_fmt("xo%d", j)};
 }
 
-static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
-                                     const jit_shape &js,
-                                     const jit_strategy &st) {
-  const int NG = ph.n_group_cols;
-  const int NL = ph.n_leaves;
-  char b[2048];
-  std::string s;
+/* per-block field mask of a stream read r entries at once */
+static void jit_v2_emit_mask(std::string &s, const jit_stream &sm, bool m32) {
+  jit_emit(s,
+           m32 ? "    const uint32_t %s = (1u << %s) - 1;\n"
+               : "    const uint64_t %s = (1ull << %s) - 1;\n",
+           sm.m.c_str(), sm.W.c_str());
+}
+
+/* the lane's R packed fields of a stream, in one read */
+static void jit_v2_emit_packed_read(std::string &s, const jit_stream &sm,
+                                    bool m32, int R) {
+  if (m32)
+    jit_emit(s,
+             "      uint32_t %s = jit_bread32(bv.base, %s + rbase * %s);\n",
+             sm.w.c_str(), sm.off.c_str(), sm.W.c_str());
+  else
+    jit_emit(s,
+             "      uint64_t %1$s = jit_bread(bv.base, %2$s + rbase * %3$s, "
+             "%4$d * %3$s);\n",
+             sm.w.c_str(), sm.off.c_str(), sm.W.c_str(), R);
+}
+
+/* row k's dict ref of a stream, clamped to the null bucket */
+static void jit_v2_emit_ref(std::string &s, const std::string &name,
+                            const std::string &count, const jit_stream &sm,
+                            bool packed) {
+  jit_emit(s,
+           "        uint32_t %1$s = (uint32_t)%2$s;\n"
+           "        if (%1$s > %3$s) %1$s = %3$s;\n",
+           name.c_str(), sm.field(packed).c_str(), count.c_str());
+}
+
+/* per-row text of a product's b or c operand on value slot j: its value
+   table's entry when the column is dict-REF (the table holds one -/+ e and
+   0 for NULL), else the CTX value with NULL as 0. sign '-' / '+' folds
+   `one` in; 0 takes the value as it is. */
+static std::string jit_v2_operand(int tab, int j, char sign, int64_t one) {
+  if (tab >= 0) return jit_fmt("vt%d[x%d]", tab, j);
+  if (!sign) return jit_fmt("(nu%1$d ? 0ll : v%1$d)", j);
+  return jit_fmt("(nu%1$d ? 0ll : (%2$lldll %3$c v%1$d))", j, (long long)one,
+                 sign);
+}
+
+static const char *jit_v2_is_min(const dev_agg &g) {
+  return g.kind == OBX_AGG_MIN ? "true" : "false";
+}
+
+/* aggregates the flush reduces in the workgroup first (facc), as bit sets */
+struct jit_v2_facc {
+  uint32_t sum = 0, min = 0, max = 0;
+  bool any() const { return (sum | min | max) != 0; }
+};
+static jit_v2_facc jit_v2_facc_of(const dev_plan_hdr &ph,
+                                  const jit_strategy &st) {
+  jit_v2_facc f;
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (st.astrat[a] == JA_HIST || st.astrat[a] == JA_HCOUNT ||
+        (st.jws_on && st.jws_member[a]))
+      f.sum |= 1u << a;
+    else if (st.astrat[a] == JA_HISTMM)
+      (ph.aggs[a].kind == OBX_AGG_MIN ? f.min : f.max) |= 1u << a;
+  }
+  return f;
+}
+
+/* ---- kernel phases, in kernel order ---- */
+
+static void jit_v2_prologue(const dev_plan_hdr &ph, const jit_shape &,
+                            const jit_strategy &st, std::string &s) {
   s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
        "#include \"obx_jit_dev.h\"\n\n";
-  snprintf(b, sizeof b,
+  jit_emit(s,
            "#define NL %d\n#define NG %d\n#define NW64 %d\n"
            "#define NAGGS %u\n#define HTOT %u\n#define NSTRIPE %u\n"
            "#define JSTAGE %u\n#define JC %u\n\n",
-           NL, NG, st.n_w64 > 0 ? st.n_w64 : 1, (unsigned)ph.n_aggs,
+           (int)ph.n_leaves, (int)ph.n_group_cols,
+           st.n_w64 > 0 ? st.n_w64 : 1, (unsigned)ph.n_aggs,
            st.hist_total > 0 ? st.hist_total : 1, (unsigned)st.stripes,
            (unsigned)st.stage_bytes, st.jcells);
-  s += b;
-  if (st.bdesc) {
-    snprintf(b, sizeof b,
+  if (st.bdesc)
+    jit_emit(s,
              "#define NBS %u\n"
              "/* what the block loop needs of one block, in registers: the\n"
              "   packed descriptor's header and column slots, and the\n"
@@ -856,9 +846,7 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "i);\n"
              "}\n\n",
              st.bd_cols.n);
-    s += b;
-  }
-  snprintf(b, sizeof b,
+  jit_emit(s,
            "/* Persistent-accumulator scan (the whole-kernel generalization\n"
            "   of the storage group-by pushdown, ObVectorStore::do_group_by):\n"
            "   the dicts are byte-identical in every micro block (verified\n"
@@ -877,42 +865,34 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
            "    unsigned long long *__restrict__ counters,\n"
            "    const obx_bdesc *__restrict__ bdesc) {\n",
            st.wpb);
-  s += b;
+}
+
+/* LDS declarations and their zeroing */
+static void jit_v2_lds(const dev_plan_hdr &ph, const jit_shape &,
+                       const jit_strategy &st, std::string &s) {
   s += "  __shared__ __attribute__((aligned(16))) uint8_t "
-       "lds_blk[JSTAGE];\n";
-  s += ""
+       "lds_blk[JSTAGE];\n"
        "  __shared__ unsigned long long wacc64[NW64][JC][NSTRIPE];\n"
        "  __shared__ uint32_t hist[HTOT];\n";
-  if (st.n_mm > 0) {
-    snprintf(b, sizeof b,
+  if (st.n_mm > 0)
+    jit_emit(s,
              "  /* CAS min/max cells: [slot][cell][val, valid] */\n"
              "  __shared__ unsigned long long wmm[%d][JC][2];\n",
              st.n_mm);
-    s += b;
-  }
-  s += ""
-       "  __shared__ uint64_t keytab[16];\n"
+  s += "  __shared__ uint64_t keytab[16];\n"
        "  __shared__ int cslot[16];\n";
-  if (st.jws_on) {
-    snprintf(b, sizeof b,
-             "  __shared__ unsigned long long jws[%uu * %uu * %uu];\n",
+  if (st.jws_on)
+    jit_emit(s, "  __shared__ unsigned long long jws[%uu * %uu * %uu];\n",
              st.jws_cells, st.jws_d0, st.jws_d1);
-    s += b;
-  }
   if (st.cnt_hist < 0)
     s += "  __shared__ uint32_t wcnt[JC][NSTRIPE];\n";
-  for (int t = 0; t < st.n_tab; t++) {
-    snprintf(b, sizeof b, "  __shared__ long long vt%d[%u];\n", t,
-             st.tabs[t].dim);
-    s += b;
-  }
-  if (st.ctab_agg >= 0) {
-    snprintf(b, sizeof b,
+  for (int t = 0; t < st.n_tab; t++)
+    jit_emit(s, "  __shared__ long long vt%d[%u];\n", t, st.tabs[t].dim);
+  if (st.ctab_agg >= 0)
+    jit_emit(s,
              "  /* combined factor table [xb][xc] of the narrowed PROD3 */\n"
              "  __shared__ uint32_t vtc[%uu * %uu];\n",
              st.ctab_db, st.ctab_dc);
-    s += b;
-  }
   s += "  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> "
        "6;\n"
        "  uint32_t lane_cnt = 0;\n"
@@ -920,35 +900,62 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "\n"
        "  for (uint32_t i = tid; i < NW64 * JC * NSTRIPE; i += WG)\n"
        "    (&wacc64[0][0][0])[i] = 0;\n";
-  if (st.n_mm > 0) {
-    /* val slot gets the is_min/is_max sentinel; valid slot 0.  The
-       per-agg sentinel depends on kind, so init per (slot,cell). */
-    for (uint32_t a = 0; a < ph.n_aggs; a++) {
-      if (st.amm[a] < 0) continue;
-      snprintf(b, sizeof b,
-               "  for (uint32_t i = tid; i < JC; i += WG) {\n"
-               "    wmm[%d][i][0] = (unsigned long long)%s;\n"
-               "    wmm[%d][i][1] = 0;\n"
-               "  }\n",
-               st.amm[a],
-               ph.aggs[a].kind == OBX_AGG_MIN ? "INT64_MAX" : "INT64_MIN",
-               st.amm[a]);
-      s += b;
-    }
+  /* val slot gets the is_min/is_max sentinel; valid slot 0.  The per-agg
+     sentinel depends on kind, so init per (slot,cell). */
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (st.amm[a] < 0) continue;
+    jit_emit(s,
+             "  for (uint32_t i = tid; i < JC; i += WG) {\n"
+             "    wmm[%1$d][i][0] = (unsigned long long)%2$s;\n"
+             "    wmm[%1$d][i][1] = 0;\n"
+             "  }\n",
+             st.amm[a],
+             ph.aggs[a].kind == OBX_AGG_MIN ? "INT64_MAX" : "INT64_MIN");
   }
-  s += ""
-       "  for (uint32_t i = tid; i < HTOT; i += WG) hist[i] = 0;\n";
-  if (st.jws_on) {
-    snprintf(b, sizeof b,
+  s += "  for (uint32_t i = tid; i < HTOT; i += WG) hist[i] = 0;\n";
+  if (st.jws_on)
+    jit_emit(s,
              "  for (uint32_t i = tid; i < %uu * %uu * %uu; i += WG)\n"
              "    jws[i] = 0;\n",
              st.jws_cells, st.jws_d0, st.jws_d1);
-    s += b;
-  }
   if (st.cnt_hist < 0)
     s += "  for (uint32_t i = tid; i < JC * NSTRIPE; i += WG)\n"
          "    (&wcnt[0][0])[i] = 0;\n";
-  /* one-time table + key builds from block 0 (dicts are identical) */
+}
+
+/* key of a group cell: column g's part, from its dict entry */
+static void jit_v2_emit_key_part(const dev_plan_hdr &ph, int g,
+                                 std::string &s) {
+  const std::string keep =
+      ph.group_len[g] >= 8
+          ? "~0ull"
+          : jit_fmt("((1ull << (8 * %u)) - 1)", (unsigned)ph.group_len[g]);
+  if (g == 0)
+    jit_emit(s,
+             "    for (uint32_t cell = tid; cell < fcells; cell += WG) {\n"
+             "      uint32_t r0 = %s;\n"
+             "      uint64_t key = 0;\n"
+             "      if (r0 >= gb0->count) key |= 1ull << 56;\n"
+             "      else {\n"
+             "        int64_t kv = dict_entry(bv0, *gb0, r0);\n"
+             "        key |= (uint64_t)kv & %s;\n"
+             "      }\n",
+             ph.n_group_cols > 1 ? "cell % fdim0" : "cell", keep.c_str());
+  else
+    jit_emit(s,
+             "      uint32_t r1 = cell / fdim0;\n"
+             "      if (r1 >= gb1->count) key |= 1ull << 57;\n"
+             "      else {\n"
+             "        int64_t kv1 = dict_entry(bv0, *gb1, r1);\n"
+             "        key |= ((uint64_t)kv1 & %s) << (8 * %u);\n"
+             "      }\n",
+             keep.c_str(), (unsigned)ph.group_len[0]);
+}
+
+/* one-time value tables and key table, from block 0 (dicts are identical) */
+static void jit_v2_tables(const dev_plan_hdr &ph, const jit_shape &js,
+                          const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
   s += "  {\n"
        "    const dev_block &b0 = blocks[0];\n"
        "    blk_view bv0;\n"
@@ -957,13 +964,11 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "    bv0.rbase_bit = 0;\n";
   for (int t = 0; t < st.n_tab; t++) {
     const jit_vtab &vt = st.tabs[t];
-    char ex[64];
-    if (vt.kind == 0) snprintf(ex, sizeof ex, "e2");
-    else if (vt.kind == 1)
-      snprintf(ex, sizeof ex, "%lldll - e2", (long long)vt.one);
-    else
-      snprintf(ex, sizeof ex, "%lldll + e2", (long long)vt.one);
-    snprintf(b, sizeof b,
+    const std::string ex =
+        vt.kind == 0 ? "e2"
+                     : jit_fmt("%lldll %c e2", (long long)vt.one,
+                               vt.kind == 1 ? '-' : '+');
+    jit_emit(s,
              "    {\n"
              "      const dev_col *tb = &b0.cols[%u];\n"
              "      for (uint32_t e = tid; e <= tb->count && e < %uu; e += "
@@ -976,78 +981,40 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "        vt%d[e] = v2;\n"
              "      }\n"
              "    }\n",
-             (unsigned)js.vcol[st.tabs[t].vc], st.tabs[t].dim, ex, t);
-    s += b;
+             (unsigned)js.vcol[vt.vc], vt.dim, ex.c_str(), t);
   }
   if (st.ctab_agg >= 0) {
     const dev_agg &g = ph.aggs[st.ctab_agg];
-    snprintf(b, sizeof b,
+    jit_emit(s,
              "    {\n"
-             "      const dev_col *tb = &b0.cols[%u], *tc = &b0.cols[%u];\n"
-             "      for (uint32_t e = tid; e < %uu * %uu; e += WG) {\n"
-             "        const uint32_t eb = e / %uu, ec = e %% %uu;\n"
+             "      const dev_col *tb = &b0.cols[%1$u], *tc = &b0.cols[%2$u];\n"
+             "      for (uint32_t e = tid; e < %3$uu * %4$uu; e += WG) {\n"
+             "        const uint32_t eb = e / %4$uu, ec = e %% %4$uu;\n"
              "        long long fb = 0, fc = 0; /* null slots: factor 0 */\n"
-             "        if (eb < tb->count) fb = %lldll - dict_entry(bv0, *tb, "
+             "        if (eb < tb->count) fb = %5$lldll - dict_entry(bv0, *tb, "
              "eb);\n"
-             "        if (ec < tc->count) fc = %lldll + dict_entry(bv0, *tc, "
+             "        if (ec < tc->count) fc = %6$lldll + dict_entry(bv0, *tc, "
              "ec);\n"
              "        vtc[e] = (uint32_t)(fb * fc);\n"
              "      }\n"
              "    }\n",
              (unsigned)ph.need_cols[g.ib], (unsigned)ph.need_cols[g.ic],
-             st.ctab_db, st.ctab_dc, st.ctab_dc, st.ctab_dc,
-             (long long)g.one_b, (long long)g.one_c);
-    s += b;
+             st.ctab_db, st.ctab_dc, (long long)g.one_b, (long long)g.one_c);
   }
   if (NG > 0) {
-    snprintf(b, sizeof b,
+    jit_emit(s,
              "    const dev_col *gb0 = &b0.cols[%u];\n"
              "    const uint32_t fdim0 = gb0->count + 1;\n",
              (unsigned)ph.need_cols[ph.group_idx[0]]);
-    s += b;
-    if (NG > 1) {
-      snprintf(b, sizeof b,
+    if (NG > 1)
+      jit_emit(s,
                "    const dev_col *gb1 = &b0.cols[%u];\n"
                "    const uint32_t fdim1 = gb1->count + 1;\n"
                "    const uint32_t fcells = fdim0 * fdim1;\n",
                (unsigned)ph.need_cols[ph.group_idx[1]]);
-      s += b;
-    } else {
+    else
       s += "    const uint32_t fcells = fdim0;\n";
-    }
-    snprintf(b, sizeof b,
-             "    for (uint32_t cell = tid; cell < fcells; cell += WG) {\n"
-             "      uint32_t r0 = %s;\n"
-             "      uint64_t key = 0;\n"
-             "      if (r0 >= gb0->count) key |= 1ull << 56;\n"
-             "      else {\n"
-             "        int64_t kv = dict_entry(bv0, *gb0, r0);\n"
-             "        key |= (uint64_t)kv & %s;\n"
-             "      }\n",
-             NG > 1 ? "cell % fdim0" : "cell",
-             ph.group_len[0] >= 8 ? "~0ull"
-                                  : "((1ull << (8 * KL0)) - 1)");
-    std::string t1(b);
-    char kl[16];
-    snprintf(kl, sizeof kl, "%u", (unsigned)ph.group_len[0]);
-    size_t p;
-    while ((p = t1.find("KL0")) != std::string::npos) t1.replace(p, 3, kl);
-    s += t1;
-    if (NG > 1) {
-      snprintf(b, sizeof b,
-               "      uint32_t r1 = cell / fdim0;\n"
-               "      if (r1 >= gb1->count) key |= 1ull << 57;\n"
-               "      else {\n"
-               "        int64_t kv1 = dict_entry(bv0, *gb1, r1);\n"
-               "        key |= ((uint64_t)kv1 & %s) << (8 * %u);\n"
-               "      }\n",
-               ph.group_len[1] >= 8 ? "~0ull" : "((1ull << (8 * KL1)) - 1)",
-               (unsigned)ph.group_len[0]);
-      std::string t2(b);
-      snprintf(kl, sizeof kl, "%u", (unsigned)ph.group_len[1]);
-      while ((p = t2.find("KL1")) != std::string::npos) t2.replace(p, 3, kl);
-      s += t2;
-    }
+    for (int g = 0; g < NG; g++) jit_v2_emit_key_part(ph, g, s);
     s += "      keytab[cell] = key;\n"
          "    }\n";
   } else {
@@ -1056,10 +1023,79 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
   s += "  }\n"
        "  __syncthreads();\n"
        "\n";
-  /* ---- block loop: stage, per-block preamble, row sweep ---- */
-  if (st.bdesc) {
-    jit_gen_block_head_bdesc(ph, js, st, s);
-  } else {
+}
+
+/* Block-loop head when the strategy reads the packed descriptor (st.bdesc):
+   verdict, stage and per-block geometry come from a jmeta in registers,
+   never from blocks[blk] -- except a CTX value column that needs a full
+   col_ctx (not raw8), which reads its dev_col as before. The jmeta is
+   loaded at the top of the iteration: scalar loads from two cache lines
+   (leaf tests, record), then the stage DMA, where dev_block cost four
+   dependent round trips over up to six lines. Loading it one block ahead,
+   behind the stage DMA, measured slower and is not carried
+   (profiles/r05_scan_bdesc.md). */
+static void jit_v2_block_head_bdesc(const dev_plan_hdr &ph,
+                                    const jit_shape &js,
+                                    const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
+  const int NL = ph.n_leaves;
+  s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
+       "gridDim.x) {\n"
+       "    jmeta cm;\n"
+       "    jit_load_meta(cm, bdesc, bleaves, blk);\n"
+       "    uint8_t blk_verdict = 1;\n";
+  for (int i = 0; i < NL; i++)
+    jit_emit(s,
+             "    {\n"
+             "      const uint8_t c = jit_leaf_class(\n"
+             "          cm.lf[%d], OBX_BD_FLAGS(cm.s[%d]));\n"
+             "      if (c == 0) blk_verdict = 0;\n"
+             "      else if (c == 2 && blk_verdict) blk_verdict = 2;\n"
+             "    }\n",
+             i, jit_bd_slot(st, st.leaf_cols[i]));
+  s += "    if (blk_verdict == 0) continue;\n"
+       "    __syncthreads(); /* drain previous block's LDS reads */\n"
+       "    stage2(buf, cm.byte, cm.len, lds_blk);\n"
+       "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+       "    __syncthreads();\n"
+       "    const uint64_t blk_bit = cm.byte * 8;\n"
+       "    blk_view bv;\n"
+       "    bv.base = lds_blk;\n"
+       "    bv.bit_bias = blk_bit;\n"
+       "    bv.rbase_bit = 0;\n"
+       "    const uint32_t rows = cm.rows;\n"
+       "\n";
+  for (int g = 0; g < NG && g < 2; g++)
+    jit_emit(s,
+             "    const uint32_t go%1$d = OBX_BD_OFF(cm.s[%2$d]);\n"
+             "    const uint32_t gW%1$d = OBX_BD_WIDTH(cm.s[%2$d]);\n"
+             "    const uint32_t gn%1$d = OBX_BD_COUNT(cm.s[%2$d]);\n",
+             g, jit_bd_slot(st, ph.need_cols[ph.group_idx[g]]));
+  if (NG > 1) s += "    const uint32_t dim0 = gn0 + 1;\n";
+  for (int j = 0; j < js.n_vc; j++) {
+    const int k = jit_bd_slot(st, js.vcol[j]);
+    if (st.vmode[j] == JV_REF)
+      jit_emit(s,
+               "    const uint32_t xo%1$d = OBX_BD_OFF(cm.s[%2$d]);\n"
+               "    const uint32_t xW%1$d = OBX_BD_WIDTH(cm.s[%2$d]);\n"
+               "    const uint32_t xn%1$d = OBX_BD_COUNT(cm.s[%2$d]);\n",
+               j, k);
+    else if (st.vraw8[j])
+      jit_emit(s, "    const uint32_t vb%d = OBX_BD_OFF(cm.s[%d]) >> 3;\n", j,
+               k);
+    else
+      jit_emit(s,
+               "    const col_ctx c%d =\n"
+               "        make_col_ctx(blocks[blk].cols[%u], blk_bit);\n",
+               j, (unsigned)js.vcol[j]);
+  }
+}
+
+/* block-loop head when the strategy reads dev_block */
+static void jit_v2_block_head_blocks(const dev_plan_hdr &ph,
+                                     const jit_shape &js,
+                                     const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
   s += "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += "
        "gridDim.x) {\n"
        "    const dev_block &cur = blocks[blk];\n"
@@ -1075,437 +1111,283 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "    __syncthreads(); /* drain previous block's LDS reads */\n"
        "    stage2(buf, cur, lds_blk);\n"
        "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-       "    __syncthreads();\n";
-  s += "    const uint64_t blk_bit = cur.block_byte * 8;\n"
+       "    __syncthreads();\n"
+       "    const uint64_t blk_bit = cur.block_byte * 8;\n"
        "    blk_view bv;\n"
        "    bv.base = lds_blk;\n"
        "    bv.bit_bias = blk_bit;\n"
        "    bv.rbase_bit = 0;\n"
        "    const uint32_t rows = cur.row_count;\n"
        "\n";
-  if (NG > 0) {
-    snprintf(b, sizeof b,
-             "    const dev_col *gd0 = &cur.cols[%u];\n"
-             "    const uint32_t go0 = (uint32_t)(gd0->data_bit - blk_bit);\n"
-             "    const uint32_t gW0 = PW(*gd0);\n"
-             "    const uint32_t gn0 = gd0->count;\n",
-             (unsigned)ph.need_cols[ph.group_idx[0]]);
-    s += b;
-  }
-  if (NG > 1) {
-    snprintf(b, sizeof b,
-             "    const dev_col *gd1 = &cur.cols[%u];\n"
-             "    const uint32_t go1 = (uint32_t)(gd1->data_bit - blk_bit);\n"
-             "    const uint32_t gW1 = PW(*gd1);\n"
-             "    const uint32_t gn1 = gd1->count;\n"
-             "    const uint32_t dim0 = gn0 + 1;\n",
-             (unsigned)ph.need_cols[ph.group_idx[1]]);
-    s += b;
+  for (int g = 0; g < NG && g < 2; g++) {
+    jit_emit(s,
+             "    const dev_col *gd%1$d = &cur.cols[%2$u];\n"
+             "    const uint32_t go%1$d = (uint32_t)(gd%1$d->data_bit - "
+             "blk_bit);\n"
+             "    const uint32_t gW%1$d = PW(*gd%1$d);\n"
+             "    const uint32_t gn%1$d = gd%1$d->count;\n",
+             g, (unsigned)ph.need_cols[ph.group_idx[g]]);
+    if (g == 1) s += "    const uint32_t dim0 = gn0 + 1;\n";
   }
   for (int j = 0; j < js.n_vc; j++) {
-    if (st.vmode[j] == JV_REF) {
-      snprintf(b, sizeof b,
-               "    const uint32_t xo%d =\n"
-               "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
-               "    const uint32_t xW%d = PW(cur.cols[%u]);\n"
-               "    const uint32_t xn%d = cur.cols[%u].count;\n",
-               j, (unsigned)js.vcol[j], j, (unsigned)js.vcol[j], j,
-               (unsigned)js.vcol[j]);
-      s += b;
-    } else if (st.vraw8[j]) {
-      snprintf(b, sizeof b,
+    const unsigned col = js.vcol[j];
+    if (st.vmode[j] == JV_REF)
+      jit_emit(s,
+               "    const uint32_t xo%1$d =\n"
+               "        (uint32_t)(cur.cols[%2$u].data_bit - blk_bit);\n"
+               "    const uint32_t xW%1$d = PW(cur.cols[%2$u]);\n"
+               "    const uint32_t xn%1$d = cur.cols[%2$u].count;\n",
+               j, col);
+    else if (st.vraw8[j])
+      jit_emit(s,
                "    const uint32_t vb%d =\n"
                "        (uint32_t)((cur.cols[%u].data_bit >> 3) - "
                "cur.block_byte);\n",
-               j, (unsigned)js.vcol[j]);
-      s += b;
-    } else {
-      snprintf(b, sizeof b,
+               j, col);
+    else
+      jit_emit(s,
                "    const col_ctx c%d = make_col_ctx(cur.cols[%u], "
                "blk_bit);\n",
-               j, (unsigned)js.vcol[j]);
-      s += b;
-    }
+               j, col);
   }
-  } /* !st.bdesc */
-  /* filter leaf preambles (always inline in v2) */
-  for (int i = 0; i < NL; i++) {
-    if (st.bdesc) {
-      const int k = jit_bd_slot(st, st.leaf_cols[i]);
-      snprintf(b, sizeof b,
-               "    const blk_leaf lb%d = jit_leaf_of(cm.lf[%d]);\n"
-               "    const uint32_t l%do = OBX_BD_OFF(cm.s[%d]);\n"
-               "    const uint32_t l%dW = OBX_BD_WIDTH(cm.s[%d]);\n",
-               i, i, i, k, i, k);
-    } else {
-      snprintf(b, sizeof b,
-               "    const blk_leaf lb%d = bl[%d];\n"
-               "    const uint32_t l%do =\n"
-               "        (uint32_t)(cur.cols[%u].data_bit - blk_bit);\n"
-               "    const uint32_t l%dW = PW(cur.cols[%u]);\n",
-               i, i, i, (unsigned)st.leaf_cols[i], i,
-               (unsigned)st.leaf_cols[i]);
-    }
-    s += b;
-    if (st.leaf_kind[i] == 1) {
-      snprintf(b, sizeof b,
-               "    const bool l%d_all = lb%d.mode == OBX_LEAF_ALL;\n", i,
-               i);
-      s += b;
-    }
-    if (st.r > 1 && st.leaf_multi[i]) {
-      if (st.leaf_m32[i])
-        snprintf(b, sizeof b,
-                 "    const uint32_t lm%d = (1u << l%dW) - 1;\n", i, i);
-      else
-        snprintf(b, sizeof b,
-                 "    const uint64_t lm%d = (1ull << l%dW) - 1;\n", i, i);
-      s += b;
-    }
-  }
-  if (st.r > 1) {
-    if (NG > 0 && st.g_multi[0])
-      s += st.g_m32[0] ? "    const uint32_t gm0 = (1u << gW0) - 1;\n"
-                          : "    const uint64_t gm0 = (1ull << gW0) - 1;\n";
-    if (NG > 1 && st.g_multi[1])
-      s += st.g_m32[1] ? "    const uint32_t gm1 = (1u << gW1) - 1;\n"
-                          : "    const uint64_t gm1 = (1ull << gW1) - 1;\n";
-    for (int j = 0; j < js.n_vc; j++)
-      if (st.v_multi[j]) {
-        if (st.v_m32[j])
-          snprintf(b, sizeof b,
-                   "    const uint32_t xm%d = (1u << xW%d) - 1;\n", j, j);
-        else
-          snprintf(b, sizeof b,
-                   "    const uint64_t xm%d = (1ull << xW%d) - 1;\n", j, j);
-        s += b;
-      }
-  }
+}
 
-  /* ---- accumulate body ---- */
-  std::string acc;
-  acc += "        lane_cnt += live ? 1u : 0u;\n";
-  acc += "        if (live) {\n";
+/* per-block leaf operands, and the field masks of every stream that is
+   read r entries at once */
+static void jit_v2_leaf_preambles(const dev_plan_hdr &ph, const jit_shape &js,
+                                  const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
+  for (int i = 0; i < (int)ph.n_leaves; i++) {
+    if (st.bdesc)
+      jit_emit(s,
+               "    const blk_leaf lb%1$d = jit_leaf_of(cm.lf[%1$d]);\n"
+               "    const uint32_t l%1$do = OBX_BD_OFF(cm.s[%2$d]);\n"
+               "    const uint32_t l%1$dW = OBX_BD_WIDTH(cm.s[%2$d]);\n",
+               i, jit_bd_slot(st, st.leaf_cols[i]));
+    else
+      jit_emit(s,
+               "    const blk_leaf lb%1$d = bl[%1$d];\n"
+               "    const uint32_t l%1$do =\n"
+               "        (uint32_t)(cur.cols[%2$u].data_bit - blk_bit);\n"
+               "    const uint32_t l%1$dW = PW(cur.cols[%2$u]);\n",
+               i, (unsigned)st.leaf_cols[i]);
+    if (st.leaf_kind[i] == JL_RANGE)
+      jit_emit(s,
+               "    const bool l%1$d_all = lb%1$d.mode == OBX_LEAF_ALL;\n", i);
+    if (st.r > 1 && st.leaf_multi[i])
+      jit_v2_emit_mask(s, jit_v2_leaf_stream(i), st.leaf_m32[i]);
+  }
+  if (st.r <= 1) return;
+  for (int g = 0; g < NG && g < 2; g++)
+    if (st.g_multi[g])
+      jit_v2_emit_mask(s, jit_v2_group_stream(g), st.g_m32[g]);
+  for (int j = 0; j < js.n_vc; j++)
+    if (st.v_multi[j])
+      jit_v2_emit_mask(s, jit_v2_value_stream(j), st.v_m32[j]);
+}
+
+/* accumulate body: what one row adds, inside the sweep's k loop */
+static void jit_v2_accumulate(const dev_plan_hdr &ph, const jit_shape &js,
+                              const jit_strategy &st, std::string &s) {
+  s += "        lane_cnt += live ? 1u : 0u;\n"
+       "        if (live) {\n";
   if (st.cnt_hist < 0)
-    acc += "          atomicAdd(&wcnt[cell][stripe], 1u);\n";
+    s += "          atomicAdd(&wcnt[cell][stripe], 1u);\n";
   for (int t = 0; t < st.n_hist; t++) {
-    int j = st.hist_vc[t];
-    snprintf(b, sizeof b,
-             "          atomicAdd(&hist[%uu + cell * %uu + x%d], 1u);\n",
+    const int j = st.hist_vc[t];
+    jit_emit(s, "          atomicAdd(&hist[%uu + cell * %uu + x%d], 1u);\n",
              st.hist_off[t], st.vdim[j], j);
-    acc += b;
   }
   if (st.jws_on) {
-    char idx[224];
     /* x is clamped to the null bucket already; when that bucket was
        dropped (non-nullable axis) clamp to the last real entry -- the
        branch is unreachable for checksum-valid refs */
-    if (st.jws_a1 >= 0)
-      snprintf(idx, sizeof idx,
-               "cell * %uu + (x%d < %uu ? x%d : %uu) * %uu + (x%d < %uu ? "
-               "x%d : %uu)",
-               st.jws_d0 * st.jws_d1, st.jws_a0, st.jws_d0, st.jws_a0,
-               st.jws_d0 - 1, st.jws_d1, st.jws_a1, st.jws_d1, st.jws_a1,
-               st.jws_d1 - 1);
-    else
-      snprintf(idx, sizeof idx, "cell * %uu + (x%d < %uu ? x%d : %uu)",
-               st.jws_d0, st.jws_a0, st.jws_d0, st.jws_a0, st.jws_d0 - 1);
-    snprintf(b, sizeof b,
-             "          if (!nu%d)\n"
-             "            atomicAdd(&jws[%s],\n"
-             "                      (unsigned long long)v%d);\n",
-             st.jws_ja, idx, st.jws_ja);
-    acc += b;
+    auto axis = [](int j, uint32_t d) {
+      return jit_fmt("(x%1$d < %2$uu ? x%1$d : %3$uu)", j, d, d - 1);
+    };
+    const std::string idx =
+        st.jws_a1 >= 0
+            ? jit_fmt("cell * %uu + %s * %uu + %s", st.jws_d0 * st.jws_d1,
+                      axis(st.jws_a0, st.jws_d0).c_str(), st.jws_d1,
+                      axis(st.jws_a1, st.jws_d1).c_str())
+            : jit_fmt("cell * %uu + %s", st.jws_d0,
+                      axis(st.jws_a0, st.jws_d0).c_str());
+    jit_emit(s,
+             "          if (!nu%1$d)\n"
+             "            atomicAdd(&jws[%2$s],\n"
+             "                      (unsigned long long)v%1$d);\n",
+             st.jws_ja, idx.c_str());
   }
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     const dev_agg &g = ph.aggs[a];
     if (st.jws_member[a]) continue; /* folded into the joint wsum */
     if (st.astrat[a] == JA_I64_COUNT) {
-      snprintf(b, sizeof b,
+      jit_emit(s,
                "          if (!nu%d)\n"
                "            atomicAdd(&wacc64[%d][cell][stripe], 1ull);\n",
                st.aval_a[a], st.wa64[a]);
-      acc += b;
       continue;
     }
     if (st.astrat[a] == JA_MM) {
-      snprintf(b, sizeof b,
-               "          if (!nu%d) {\n"
-               "            cas_minmax(&wmm[%d][cell][0], v%d, %s);\n"
-               "            wmm[%d][cell][1] = 1;\n"
+      jit_emit(s,
+               "          if (!nu%1$d) {\n"
+               "            cas_minmax(&wmm[%2$d][cell][0], v%1$d, %3$s);\n"
+               "            wmm[%2$d][cell][1] = 1;\n"
                "          }\n",
-               st.aval_a[a], st.amm[a], st.aval_a[a],
-               g.kind == OBX_AGG_MIN ? "true" : "false", st.amm[a]);
-      acc += b;
+               st.aval_a[a], st.amm[a], jit_v2_is_min(g));
       continue;
     }
     if (st.astrat[a] != JA_I64) continue;
-    int ja = st.aval_a[a];
-    char va[64];
-    if (st.atab_a[a] >= 0)
-      snprintf(va, sizeof va, "vt%d[x%d]", st.atab_a[a], ja);
-    else
-      snprintf(va, sizeof va, "v%d", ja);
-    auto slot_lookup = [&](uint8_t need_idx) -> int {
-      for (int j2 = 0; j2 < js.n_vc; j2++)
-        if (js.vcol[j2] == ph.need_cols[need_idx]) return j2;
-      return -1;
-    };
+    const int ja = st.aval_a[a], jb = js.slot(ph, g.ib),
+              jc = js.slot(ph, g.ic);
+    const std::string va = st.atab_a[a] >= 0
+                               ? jit_fmt("vt%d[x%d]", st.atab_a[a], ja)
+                               : jit_fmt("v%d", ja);
     switch (g.kind) {
       case OBX_AGG_SUM:
-        snprintf(b, sizeof b,
+        jit_emit(s,
                  "          atomicAdd(&wacc64[%d][cell][stripe],\n"
                  "                    (unsigned long long)%s);\n",
-                 st.wa64[a], va);
-        acc += b;
+                 st.wa64[a], va.c_str());
         break;
-      case OBX_AGG_SUM_MUL: {
-        int jb = slot_lookup(g.ib);
-        char vb[64];
-        if (st.atab_b[a] >= 0)
-          snprintf(vb, sizeof vb, "vt%d[x%d]", st.atab_b[a], jb);
-        else
-          snprintf(vb, sizeof vb, "(nu%d ? 0ll : v%d)", jb, jb);
-        snprintf(b, sizeof b,
+      case OBX_AGG_SUM_MUL:
+        jit_emit(s,
                  "          atomicAdd(&wacc64[%d][cell][stripe],\n"
                  "                    (unsigned long long)((long long)%s * "
                  "%s));\n",
-                 st.wa64[a], va, vb);
-        acc += b;
+                 st.wa64[a], va.c_str(),
+                 jit_v2_operand(st.atab_b[a], jb, 0, 0).c_str());
         break;
-      }
-      case OBX_AGG_SUM_PROD2: {
-        int jb = slot_lookup(g.ib);
-        char vb[64];
-        if (st.atab_b[a] >= 0)
-          snprintf(vb, sizeof vb, "vt%d[x%d]", st.atab_b[a], jb);
-        else
-          snprintf(vb, sizeof vb, "(nu%d ? 0ll : (%lldll - v%d))", jb,
-                   (long long)g.one_b, jb);
-        snprintf(b, sizeof b,
-                 "          long long p2_%u = (long long)%s * %s;\n"
-                 "          atomicAdd(&wacc64[%d][cell][stripe],\n"
-                 "                    (unsigned long long)p2_%u);\n",
-                 a, va, vb, st.wa64[a], a);
-        acc += b;
+      case OBX_AGG_SUM_PROD2:
+        jit_emit(s,
+                 "          long long p2_%1$u = (long long)%2$s * %3$s;\n"
+                 "          atomicAdd(&wacc64[%4$d][cell][stripe],\n"
+                 "                    (unsigned long long)p2_%1$u);\n",
+                 a, va.c_str(),
+                 jit_v2_operand(st.atab_b[a], jb, '-', g.one_b).c_str(),
+                 st.wa64[a]);
         if ((js.agg_f2 & (1u << a)) && !st.jws_member[a + 1]) {
           const dev_agg &g3 = ph.aggs[a + 1];
-          int jc = slot_lookup(g3.ic);
-          char vc[64];
-          if (st.atab_c[a + 1] >= 0)
-            snprintf(vc, sizeof vc, "vt%d[x%d]", st.atab_c[a + 1], jc);
-          else
-            snprintf(vc, sizeof vc, "(nu%d ? 0ll : (%lldll + v%d))", jc,
-                     (long long)g3.one_c, jc);
-          snprintf(b, sizeof b,
+          jit_emit(s,
                    "          atomicAdd(&wacc64[%d][cell][stripe],\n"
                    "                    (unsigned long long)(p2_%u * "
                    "%s));\n",
-                   st.wa64[a + 1], a, vc);
-          acc += b;
+                   st.wa64[a + 1], a,
+                   jit_v2_operand(st.atab_c[a + 1], js.slot(ph, g3.ic), '+',
+                                  g3.one_c)
+                       .c_str());
         }
         break;
-      }
-      case OBX_AGG_SUM_PROD3: {
+      case OBX_AGG_SUM_PROD3:
         /* fused into the preceding PROD2's emission — unless that agg
            became a JWS member and skipped its per-row code entirely */
-        if (a > 0 && (js.agg_f2 & (1u << (a - 1))) &&
-            !st.jws_member[a - 1])
+        if (a > 0 && (js.agg_f2 & (1u << (a - 1))) && !st.jws_member[a - 1])
           break;
-        int jb = slot_lookup(g.ib), jc = slot_lookup(g.ic);
         if (st.ctab_agg == (int)a) {
-          snprintf(b, sizeof b,
+          jit_emit(s,
                    "          atomicAdd(&wacc64[%d][cell][stripe],\n"
                    "                    (unsigned long long)(uint32_t)v%d *\n"
                    "                        (unsigned long long)vtc[x%d * %uu "
                    "+ x%d]);\n",
                    st.wa64[a], ja, jb, st.ctab_dc, jc);
-          acc += b;
           break;
         }
-        char vb[64], vc[64];
-        if (st.atab_b[a] >= 0)
-          snprintf(vb, sizeof vb, "vt%d[x%d]", st.atab_b[a], jb);
-        else
-          snprintf(vb, sizeof vb, "(nu%d ? 0ll : (%lldll - v%d))", jb,
-                   (long long)g.one_b, jb);
-        if (st.atab_c[a] >= 0)
-          snprintf(vc, sizeof vc, "vt%d[x%d]", st.atab_c[a], jc);
-        else
-          snprintf(vc, sizeof vc, "(nu%d ? 0ll : (%lldll + v%d))", jc,
-                   (long long)g.one_c, jc);
-        snprintf(b, sizeof b,
+        jit_emit(s,
                  "          atomicAdd(&wacc64[%d][cell][stripe],\n"
                  "                    (unsigned long long)((long long)%s * "
                  "%s * %s));\n",
-                 st.wa64[a], va, vb, vc);
-        acc += b;
+                 st.wa64[a], va.c_str(),
+                 jit_v2_operand(st.atab_b[a], jb, '-', g.one_b).c_str(),
+                 jit_v2_operand(st.atab_c[a], jc, '+', g.one_c).c_str());
         break;
-      }
     }
   }
-  acc += "        }\n";
+  s += "        }\n";
+}
 
-  /* ---- row sweep (strip-mined; whole WG over the block) ---- */
-  int R = st.r > 0 ? st.r : 1;
-  snprintf(b, sizeof b,
-           "    const uint32_t itersR = (rows + WG * %d - 1) / (WG * %d);\n"
+/* row sweep (strip-mined; whole WG over the block), to the end of the
+   block loop */
+static void jit_v2_sweep(const dev_plan_hdr &ph, const jit_shape &js,
+                         const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
+  const int NL = ph.n_leaves;
+  const int R = st.r > 0 ? st.r : 1;
+  jit_emit(s,
+           "    const uint32_t itersR = (rows + WG * %1$d - 1) / (WG * %1$d);\n"
            "    for (uint32_t it = 0; it < itersR; it++) {\n"
-           "      const uint32_t rbase = (it * WG + tid) * %d;\n",
-           R, R, R);
-  s += b;
+           "      const uint32_t rbase = (it * WG + tid) * %1$d;\n",
+           R);
   for (int i = 0; i < NL; i++)
-    if (st.leaf_multi[i]) {
-      if (st.leaf_m32[i])
-        snprintf(b, sizeof b,
-                 "      uint32_t wl%d = jit_bread32(bv.base, l%do + rbase * "
-                 "l%dW);\n",
-                 i, i, i);
-      else
-        snprintf(b, sizeof b,
-                 "      uint64_t wl%d = jit_bread(bv.base, l%do + rbase * "
-                 "l%dW, %d * l%dW);\n",
-                 i, i, i, R, i);
-      s += b;
-    }
-  for (int g2 = 0; g2 < NG && g2 < 2; g2++) {
-    if (!st.g_multi[g2]) continue;
-    if (st.g_m32[g2])
-      snprintf(b, sizeof b,
-               "      uint32_t wgr%d = jit_bread32(bv.base, go%d + rbase * "
-               "gW%d);\n",
-               g2, g2, g2);
-    else
-      snprintf(b, sizeof b,
-               "      uint64_t wgr%d = jit_bread(bv.base, go%d + rbase * "
-               "gW%d, %d * gW%d);\n",
-               g2, g2, g2, R, g2);
-    s += b;
-  }
+    if (st.leaf_multi[i])
+      jit_v2_emit_packed_read(s, jit_v2_leaf_stream(i), st.leaf_m32[i], R);
+  for (int g = 0; g < NG && g < 2; g++)
+    if (st.g_multi[g])
+      jit_v2_emit_packed_read(s, jit_v2_group_stream(g), st.g_m32[g], R);
   for (int j = 0; j < js.n_vc; j++)
-    if (st.v_multi[j]) {
-      if (st.v_m32[j])
-        snprintf(b, sizeof b,
-                 "      uint32_t wx%d = jit_bread32(bv.base, xo%d + rbase * "
-                 "xW%d);\n",
-                 j, j, j);
-      else
-        snprintf(b, sizeof b,
-                 "      uint64_t wx%d = jit_bread(bv.base, xo%d + rbase * "
-                 "xW%d, %d * xW%d);\n",
-                 j, j, j, R, j);
-      s += b;
-    }
+    if (st.v_multi[j])
+      jit_v2_emit_packed_read(s, jit_v2_value_stream(j), st.v_m32[j], R);
   for (int j = 0; j < js.n_vc; j++)
-    if (st.vmode[j] == JV_CTX && st.vraw8[j]) {
-      snprintf(b, sizeof b,
-               "      const uint8_t *ep%d = bv.base + vb%d + (rbase << "
+    if (st.vmode[j] == JV_CTX && st.vraw8[j])
+      jit_emit(s,
+               "      const uint8_t *ep%1$d = bv.base + vb%1$d + (rbase << "
                "3);\n",
-               j, j);
-      s += b;
-    }
-  snprintf(b, sizeof b,
+               j);
+  jit_emit(s,
            "#pragma unroll\n"
            "      for (uint32_t k = 0; k < %du; k++) {\n"
            "        const uint32_t r = rbase + k;\n"
            "        bool live = r < rows;\n",
            R);
-  s += b;
   for (int i = 0; i < NL; i++) {
-    if (st.leaf_kind[i] == 1) {
-      if (st.leaf_multi[i])
-        snprintf(b, sizeof b,
-                 "        if (live && !l%d_all) {\n"
-                 "          uint64_t v = ((wl%d >> (k * l%dW)) & lm%d) ^ "
-                 "lb%d.mask;\n"
-                 "          live = ((v - lb%d.lo) <= (lb%d.hi - lb%d.lo)) "
-                 "!= (bool)lb%d.invert;\n"
-                 "        }\n",
-                 i, i, i, i, i, i, i, i, i);
-      else
-        snprintf(b, sizeof b,
-                 "        if (live && !l%d_all) {\n"
-                 "          uint64_t v = jit_bread(bv.base, l%do + r * "
-                 "l%dW, l%dW) ^ lb%d.mask;\n"
-                 "          live = ((v - lb%d.lo) <= (lb%d.hi - lb%d.lo)) "
-                 "!= (bool)lb%d.invert;\n"
-                 "        }\n",
-                 i, i, i, i, i, i, i, i, i);
-    } else {
-      if (st.leaf_multi[i])
-        snprintf(b, sizeof b,
-                 "        if (live)\n"
-                 "          live = (lb%d.mask >>\n"
-                 "                  (uint32_t)((wl%d >> (k * l%dW)) & "
-                 "lm%d)) & 1;\n",
-                 i, i, i, i);
-      else
-        snprintf(b, sizeof b,
-                 "        if (live)\n"
-                 "          live = (lb%d.mask >>\n"
-                 "                  (uint32_t)jit_bread(bv.base, l%do + r "
-                 "* l%dW, l%dW)) & 1;\n",
-                 i, i, i, i);
-    }
-    s += b;
+    const jit_leaf_ops lb = {i,
+                             jit_fmt("lb%d.mask", i),
+                             jit_fmt("lb%d.lo", i),
+                             jit_fmt("lb%d.hi", i),
+                             jit_fmt("lb%d.invert", i),
+                             ""};
+    const std::string f = jit_v2_leaf_stream(i).field(st.leaf_multi[i] != 0);
+    if (st.leaf_kind[i] == JL_RANGE) jit_emit_range_test(s, 8, lb, f, true);
+    else jit_emit_mask_test(s, 8, lb, f, true);
   }
-  if (NG > 0) {
-    if (st.r > 1 && st.g_multi[0])
-      s += "        uint32_t ref0 = (uint32_t)((wgr0 >> (k * gW0)) & "
-           "gm0);\n";
-    else
-      s += "        uint32_t ref0 = (uint32_t)jit_bread(bv.base, go0 + r * "
-           "gW0, gW0);\n";
-    s += "        if (ref0 > gn0) ref0 = gn0;\n"
-         "        uint32_t cell = ref0;\n";
-  }
-  if (NG > 1) {
-    if (st.r > 1 && st.g_multi[1])
-      s += "        uint32_t ref1 = (uint32_t)((wgr1 >> (k * gW1)) & "
-           "gm1);\n";
-    else
-      s += "        uint32_t ref1 = (uint32_t)jit_bread(bv.base, go1 + r * "
-           "gW1, gW1);\n";
-    s += "        if (ref1 > gn1) ref1 = gn1;\n"
-         "        cell += ref1 * dim0;\n";
+  for (int g = 0; g < NG && g < 2; g++) {
+    jit_v2_emit_ref(s, jit_fmt("ref%d", g), jit_fmt("gn%d", g),
+                    jit_v2_group_stream(g), st.r > 1 && st.g_multi[g]);
+    s += g ? "        cell += ref1 * dim0;\n" : "        uint32_t cell = ref0;\n";
   }
   if (NG == 0) s += "        const uint32_t cell = 0;\n";
   for (int j = 0; j < js.n_vc; j++) {
-    if (st.vmode[j] == JV_REF) {
-      if (st.v_multi[j])
-        snprintf(b, sizeof b,
-                 "        uint32_t x%d = (uint32_t)((wx%d >> (k * xW%d)) & "
-                 "xm%d);\n"
-                 "        if (x%d > xn%d) x%d = xn%d;\n",
-                 j, j, j, j, j, j, j, j);
-      else
-        snprintf(b, sizeof b,
-                 "        uint32_t x%d = (uint32_t)jit_bread(bv.base, xo%d "
-                 "+ r * xW%d, xW%d);\n"
-                 "        if (x%d > xn%d) x%d = xn%d;\n",
-                 j, j, j, j, j, j, j, j);
-      s += b;
-    } else if (st.vraw8[j]) {
-      snprintf(b, sizeof b,
-               "        int64_t v%d = *(const int64_t *)(ep%d + (k << "
+    if (st.vmode[j] == JV_REF)
+      jit_v2_emit_ref(s, jit_fmt("x%d", j), jit_fmt("xn%d", j),
+                      jit_v2_value_stream(j), st.v_multi[j] != 0);
+    else if (st.vraw8[j])
+      jit_emit(s,
+               "        int64_t v%1$d = *(const int64_t *)(ep%1$d + (k << "
                "3));\n"
-               "        const bool nu%d = false;\n"
-               "        (void)nu%d;\n",
-               j, j, j, j);
-      s += b;
-    } else {
-      snprintf(b, sizeof b,
-               "        bool nu%d;\n"
-               "        int64_t v%d = ctx_value(bv, c%d, r, nu%d);\n"
-               "        (void)nu%d;\n",
-               j, j, j, j, j);
-      s += b;
-    }
+               "        const bool nu%1$d = false;\n"
+               "        (void)nu%1$d;\n",
+               j);
+    else
+      jit_emit(s,
+               "        bool nu%1$d;\n"
+               "        int64_t v%1$d = ctx_value(bv, c%1$d, r, nu%1$d);\n"
+               "        (void)nu%1$d;\n",
+               j);
   }
-  s += acc;
+  jit_v2_accumulate(ph, js, st, s);
   s += "      }\n"
        "    } /* row sweep */\n"
        "  } /* blocks */\n";
+}
+
+/* Hierarchical flush: everything summed over dict refs or joint-cell
+   slices (passes 2 and 3) is first reduced inside the workgroup, in exact
+   int128 in LDS, so each workgroup sends ONE global accumulate per (cell,
+   aggregate) instead of one per ref -- the per-ref form put ~87
+   same-address L2 atomics per live cell per workgroup on four slots. The
+   partials live in the stage buffer, which is idle by now. */
+static void jit_v2_flush_head(const dev_plan_hdr &ph, const jit_shape &,
+                              const jit_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
   s += "\n"
        "\n"
        "  /* survivor count: wave-reduce, then stripe the global atomic\n"
@@ -1518,39 +1400,18 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "  __syncthreads(); /* all accumulators final: flush once */\n"
        "\n"
        "  const dev_block &b0 = blocks[0];\n";
-  if (NG > 0) {
-    snprintf(b, sizeof b,
-             "  const uint32_t fdim0 = b0.cols[%u].count + 1;\n",
+  if (NG > 0)
+    jit_emit(s, "  const uint32_t fdim0 = b0.cols[%u].count + 1;\n",
              (unsigned)ph.need_cols[ph.group_idx[0]]);
-    s += b;
-  }
-  if (NG > 1) {
-    snprintf(b, sizeof b,
-             "  const uint32_t fcells = fdim0 * (b0.cols[%u].count + 1);\n",
+  if (NG > 1)
+    jit_emit(s, "  const uint32_t fcells = fdim0 * (b0.cols[%u].count + 1);\n",
              (unsigned)ph.need_cols[ph.group_idx[1]]);
-    s += b;
-  } else if (NG == 1) {
-    s += "  const uint32_t fcells = fdim0;\n";
-  } else {
-    s += "  const uint32_t fcells = 1;\n";
-  }
-  /* Hierarchical flush: everything summed over dict refs or joint-cell
-     slices (passes 2 and 3) is first reduced inside the workgroup, in
-     exact int128 in LDS, so each workgroup sends ONE global accumulate per
-     (cell, aggregate) instead of one per ref -- the per-ref form put ~87
-     same-address L2 atomics per live cell per workgroup on four slots.
-     The partials live in the stage buffer, which is idle by now. */
-  uint32_t f_sum = 0, f_min = 0, f_max = 0; /* aggregates going via facc */
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (st.astrat[a] == JA_HIST || st.astrat[a] == JA_HCOUNT ||
-        (st.jws_on && st.jws_member[a]))
-      f_sum |= 1u << a;
-    else if (st.astrat[a] == JA_HISTMM)
-      (ph.aggs[a].kind == OBX_AGG_MIN ? f_min : f_max) |= 1u << a;
-  }
-  const bool f_any = (f_sum | f_min | f_max) != 0;
-  if (f_any) {
-    snprintf(b, sizeof b,
+  else
+    s += NG == 1 ? "  const uint32_t fcells = fdim0;\n"
+                 : "  const uint32_t fcells = 1;\n";
+  const jit_v2_facc f = jit_v2_facc_of(ph, st);
+  if (f.any())
+    jit_emit(s,
              "  /* workgroup partials [cell][agg]: {lo, hi} of an int128\n"
              "     sum, or {value, valid} of a min/max */\n"
              "  unsigned long long (*facc)[NAGGS][2] =\n"
@@ -1563,20 +1424,23 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "                             : 0ull;\n"
              "    facc[i / NAGGS][a][1] = 0;\n"
              "  }\n",
-             f_min, f_max);
-    s += b;
-  }
+             f.min, f.max);
+}
+
+/* flush pass 1: per-cell counts, keys -> global slots, and everything
+   that is one value per cell (COUNT(*), i64 windows, CAS min/max) */
+static void jit_v2_flush_cells(const dev_plan_hdr &ph, const jit_shape &,
+                               const jit_strategy &st, std::string &s) {
   s += "  /* flush pass 1: per-cell counts, keys -> global slots */\n"
        "  for (uint32_t cell = tid; cell < fcells; cell += WG) {\n"
        "    int ce = -1;\n";
   if (st.cnt_hist >= 0) {
-    int j = st.hist_vc[st.cnt_hist];
-    snprintf(b, sizeof b,
+    const int j = st.hist_vc[st.cnt_hist];
+    jit_emit(s,
              "    unsigned long long cnt2 = 0;\n"
-             "    for (uint32_t ref = 0; ref < %uu; ref++)\n"
-             "      cnt2 += hist[%uu + cell * %uu + ref];\n",
-             st.vdim[j], st.hist_off[st.cnt_hist], st.vdim[j]);
-    s += b;
+             "    for (uint32_t ref = 0; ref < %1$uu; ref++)\n"
+             "      cnt2 += hist[%2$uu + cell * %1$uu + ref];\n",
+             st.vdim[j], st.hist_off[st.cnt_hist]);
   } else {
     s += "    unsigned long long cnt2 = 0;\n"
          "    for (uint32_t s2 = 0; s2 < NSTRIPE; s2++)\n"
@@ -1587,17 +1451,13 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "      if (gi >= 0) {\n"
        "        atomicAdd(&gtable[gi].count, cnt2);\n"
        "        ce = gi;\n";
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (st.astrat[a] == JA_COUNT_STAR) {
-      snprintf(b, sizeof b,
-               "        g_acc_i128(gtable[gi].cells[%u], cnt2, 0);\n",
+  for (uint32_t a = 0; a < ph.n_aggs; a++)
+    if (st.astrat[a] == JA_COUNT_STAR)
+      jit_emit(s, "        g_acc_i128(gtable[gi].cells[%u], cnt2, 0);\n",
                (unsigned)a);
-      s += b;
-    }
-  }
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     if (st.wa64[a] < 0) continue;
-    snprintf(b, sizeof b,
+    jit_emit(s,
              "        {\n"
              "          unsigned long long t64 = 0;\n"
              "          for (uint32_t s2 = 0; s2 < NSTRIPE; s2++)\n"
@@ -1608,20 +1468,16 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "                       (uint64_t)(v64 >> 63));\n"
              "        }\n",
              st.wa64[a], (unsigned)a);
-    s += b;
   }
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     if (st.amm[a] < 0) continue;
-    snprintf(b, sizeof b,
-             "        if (wmm[%d][cell][1]) {\n"
-             "          cas_minmax(&gtable[gi].cells[%u][0],\n"
-             "                     (int64_t)wmm[%d][cell][0], %s);\n"
-             "          gtable[gi].cells[%u][1] = 1;\n"
+    jit_emit(s,
+             "        if (wmm[%1$d][cell][1]) {\n"
+             "          cas_minmax(&gtable[gi].cells[%2$u][0],\n"
+             "                     (int64_t)wmm[%1$d][cell][0], %3$s);\n"
+             "          gtable[gi].cells[%2$u][1] = 1;\n"
              "        }\n",
-             st.amm[a], (unsigned)a, st.amm[a],
-             ph.aggs[a].kind == OBX_AGG_MIN ? "true" : "false",
-             (unsigned)a);
-    s += b;
+             st.amm[a], (unsigned)a, jit_v2_is_min(ph.aggs[a]));
   }
   s += "      } else {\n"
        "        atomicAdd(&counters[1], cnt2);\n"
@@ -1629,44 +1485,43 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
        "    }\n"
        "    cslot[cell] = ce;\n"
        "  }\n"
-       "  __syncthreads();\n"
-       "  /* flush pass 2: histogram-weighted aggregates over (cell, ref) "
+       "  __syncthreads();\n";
+}
+
+/* flush pass 2: histogram-weighted aggregates over (cell, ref) */
+static void jit_v2_flush_hists(const dev_plan_hdr &ph, const jit_shape &js,
+                               const jit_strategy &st, std::string &s) {
+  s += "  /* flush pass 2: histogram-weighted aggregates over (cell, ref) "
        "*/\n";
   for (int t = 0; t < st.n_hist; t++) {
-    int j = st.hist_vc[t];
-    bool any = false;
-    for (uint32_t a = 0; a < ph.n_aggs; a++)
-      if (st.ahist[a] == t &&
-          (st.astrat[a] == JA_HIST || st.astrat[a] == JA_HCOUNT ||
-           st.astrat[a] == JA_HISTMM))
+    const int j = st.hist_vc[t];
+    bool any = false, need_entry = false;
+    for (uint32_t a = 0; a < ph.n_aggs; a++) {
+      if (st.ahist[a] != t) continue;
+      if (st.astrat[a] == JA_HIST || st.astrat[a] == JA_HCOUNT ||
+          st.astrat[a] == JA_HISTMM)
         any = true;
+      if (st.astrat[a] == JA_HIST) need_entry = true;
+    }
     if (!any) continue;
-    snprintf(b, sizeof b,
+    jit_emit(s,
              "  {\n"
-             "    const uint32_t hcnt = b0.cols[%u].count;\n"
-             "    for (uint32_t idx = tid; idx < fcells * %uu; idx += WG) "
+             "    const uint32_t hcnt = b0.cols[%1$u].count;\n"
+             "    for (uint32_t idx = tid; idx < fcells * %2$uu; idx += WG) "
              "{\n"
-             "      uint32_t cell = idx / %uu, ref = idx %% %uu;\n"
+             "      uint32_t cell = idx / %2$uu, ref = idx %% %2$uu;\n"
              "      int ce = cslot[cell];\n"
              "      if (ce < 0 || ref >= hcnt) continue; /* excl. null "
              "bucket */\n"
-             "      uint32_t c2 = hist[%uu + cell * %uu + ref];\n"
+             "      uint32_t c2 = hist[%3$uu + cell * %2$uu + ref];\n"
              "      if (!c2) continue;\n",
-             (unsigned)js.vcol[j], st.vdim[j], st.vdim[j], st.vdim[j],
-             st.hist_off[t], st.vdim[j]);
-    s += b;
-    bool need_entry = false;
-    for (uint32_t a = 0; a < ph.n_aggs; a++)
-      if (st.ahist[a] == t && st.astrat[a] == JA_HIST) need_entry = true;
-    if (need_entry) {
-      snprintf(b, sizeof b, "      long long ev = vt%d[ref];\n",
-               st.hist_tab[t]);
-      s += b;
-    }
+             (unsigned)js.vcol[j], st.vdim[j], st.hist_off[t]);
+    if (need_entry)
+      jit_emit(s, "      long long ev = vt%d[ref];\n", st.hist_tab[t]);
     for (uint32_t a = 0; a < ph.n_aggs; a++) {
       if (st.ahist[a] != t) continue;
-      if (st.astrat[a] == JA_HIST) {
-        snprintf(b, sizeof b,
+      if (st.astrat[a] == JA_HIST)
+        jit_emit(s,
                  "      {\n"
                  "        __int128 p = (__int128)ev * (long long)c2;\n"
                  "        i128v pv = {(uint64_t)p,\n"
@@ -1675,108 +1530,93 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
                  "        lds_acc_i128(facc[cell][%u], pv);\n"
                  "      }\n",
                  (unsigned)a);
-        s += b;
-      } else if (st.astrat[a] == JA_HISTMM) {
-        /* any live dict entry bounds the min/max */
-        snprintf(b, sizeof b,
+      else if (st.astrat[a] == JA_HISTMM) /* any live entry bounds it */
+        jit_emit(s,
                  "      {\n"
-                 "        cas_minmax(&facc[cell][%u][0],\n"
-                 "                   (int64_t)vt%d[ref], %s);\n"
-                 "        facc[cell][%u][1] = 1;\n"
+                 "        cas_minmax(&facc[cell][%1$u][0],\n"
+                 "                   (int64_t)vt%2$d[ref], %3$s);\n"
+                 "        facc[cell][%1$u][1] = 1;\n"
                  "      }\n",
-                 (unsigned)a, st.atab_a[a],
-                 ph.aggs[a].kind == OBX_AGG_MIN ? "true" : "false",
-                 (unsigned)a);
-        s += b;
-      } else { /* JA_HCOUNT */
-        snprintf(b, sizeof b,
+                 (unsigned)a, st.atab_a[a], jit_v2_is_min(ph.aggs[a]));
+      else /* JA_HCOUNT */
+        jit_emit(s,
                  "      atomicAdd(&facc[cell][%u][0], (unsigned long "
                  "long)c2);\n",
                  (unsigned)a);
-        s += b;
-      }
     }
     s += "    }\n"
          "  }\n";
   }
-  /* flush pass 3: joint weighted cells -> member aggregates.
-     One (cell, d0) slice per thread; the d1 ring is reduced in
-     registers, factor products applied in int128 (exact: the per-cell
-     i64 bound is enforced at strategy build). */
-  if (st.jws_on) {
-    snprintf(b, sizeof b,
-             "  for (uint32_t idx = tid; idx < fcells * %uu; idx += WG) "
-             "{\n"
-             "    uint32_t cell = idx / %uu, d0 = idx %% %uu;\n"
-             "    int ce = cslot[cell];\n"
-             "    if (ce < 0) continue;\n"
-             "    long long s_pl = 0;\n",
-             st.jws_d0, st.jws_d0, st.jws_d0);
-    s += b;
-    /* distinct axis-1 factor tables among members */
-    int c_tabs[OBX_DEV_MAX_AGGS], n_ct = 0;
-    for (uint32_t a = 0; a < ph.n_aggs; a++) {
-      if (!st.jws_member[a] || st.jws_f1[a] < 0) continue;
-      bool seen = false;
-      for (int q = 0; q < n_ct; q++) seen |= c_tabs[q] == st.jws_f1[a];
-      if (!seen) c_tabs[n_ct++] = st.jws_f1[a];
-    }
-    for (int q = 0; q < n_ct; q++) {
-      snprintf(b, sizeof b, "    __int128 s_c%d = 0;\n", c_tabs[q]);
-      s += b;
-    }
-    snprintf(b, sizeof b,
-             "    for (uint32_t d1 = 0; d1 < %uu; d1++) {\n"
-             "      long long w = (long long)jws[cell * %uu + d0 * %uu + "
-             "d1];\n"
-             "      if (!w) continue;\n"
-             "      s_pl += w;\n",
-             st.jws_d1, st.jws_d0 * st.jws_d1, st.jws_d1);
-    s += b;
-    for (int q = 0; q < n_ct; q++) {
-      snprintf(b, sizeof b,
-               "      s_c%d += (__int128)vt%d[d1] * w;\n", c_tabs[q],
-               c_tabs[q]);
-      s += b;
-    }
-    s += "    }\n"
-         "    if (s_pl";
-    for (int q = 0; q < n_ct; q++) {
-      snprintf(b, sizeof b, " || s_c%d != 0", c_tabs[q]);
-      s += b;
-    }
-    s += ") {\n";
-    for (uint32_t a = 0; a < ph.n_aggs; a++) {
-      if (!st.jws_member[a]) continue;
-      char expr[128];
-      if (st.jws_f0[a] >= 0 && st.jws_f1[a] >= 0)
-        snprintf(expr, sizeof expr, "(__int128)vt%d[d0] * s_c%d",
-                 st.jws_f0[a], st.jws_f1[a]);
-      else if (st.jws_f0[a] >= 0)
-        snprintf(expr, sizeof expr, "(__int128)vt%d[d0] * s_pl",
-                 st.jws_f0[a]);
-      else if (st.jws_f1[a] >= 0)
-        snprintf(expr, sizeof expr, "s_c%d", st.jws_f1[a]);
-      else
-        snprintf(expr, sizeof expr, "(__int128)s_pl");
-      snprintf(b, sizeof b,
-               "      {\n"
-               "        __int128 p = %s;\n"
-               "        if (p != 0) {\n"
-               "          i128v pv = {(uint64_t)p,\n"
-               "                      (uint64_t)((unsigned __int128)p >> "
-               "64)};\n"
-               "          lds_acc_i128(facc[cell][%u], pv);\n"
-               "        }\n"
-               "      }\n",
-               expr, (unsigned)a);
-      s += b;
-    }
-    s += "    }\n"
-         "  }\n";
+}
+
+/* flush pass 3: joint weighted cells -> member aggregates. One (cell, d0)
+   slice per thread; the d1 ring is reduced in registers, factor products
+   applied in int128 (exact: the per-cell i64 bound is enforced at strategy
+   build). */
+static void jit_v2_flush_joint(const dev_plan_hdr &ph, const jit_shape &,
+                               const jit_strategy &st, std::string &s) {
+  if (!st.jws_on) return;
+  jit_emit(s,
+           "  for (uint32_t idx = tid; idx < fcells * %1$uu; idx += WG) "
+           "{\n"
+           "    uint32_t cell = idx / %1$uu, d0 = idx %% %1$uu;\n"
+           "    int ce = cslot[cell];\n"
+           "    if (ce < 0) continue;\n"
+           "    long long s_pl = 0;\n",
+           st.jws_d0);
+  /* distinct axis-1 factor tables among members */
+  int c_tabs[OBX_DEV_MAX_AGGS], n_ct = 0;
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (!st.jws_member[a] || st.jws_f1[a] < 0) continue;
+    bool seen = false;
+    for (int q = 0; q < n_ct; q++) seen |= c_tabs[q] == st.jws_f1[a];
+    if (!seen) c_tabs[n_ct++] = st.jws_f1[a];
   }
-  if (f_any) {
-    snprintf(b, sizeof b,
+  for (int q = 0; q < n_ct; q++)
+    jit_emit(s, "    __int128 s_c%d = 0;\n", c_tabs[q]);
+  jit_emit(s,
+           "    for (uint32_t d1 = 0; d1 < %1$uu; d1++) {\n"
+           "      long long w = (long long)jws[cell * %2$uu + d0 * %1$uu + "
+           "d1];\n"
+           "      if (!w) continue;\n"
+           "      s_pl += w;\n",
+           st.jws_d1, st.jws_d0 * st.jws_d1);
+  for (int q = 0; q < n_ct; q++)
+    jit_emit(s, "      s_c%1$d += (__int128)vt%1$d[d1] * w;\n", c_tabs[q]);
+  s += "    }\n"
+       "    if (s_pl";
+  for (int q = 0; q < n_ct; q++) jit_emit(s, " || s_c%d != 0", c_tabs[q]);
+  s += ") {\n";
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (!st.jws_member[a]) continue;
+    const int f0 = st.jws_f0[a], f1 = st.jws_f1[a];
+    const std::string sum = f1 >= 0 ? jit_fmt("s_c%d", f1) : "s_pl";
+    const std::string expr =
+        f0 >= 0   ? jit_fmt("(__int128)vt%d[d0] * %s", f0, sum.c_str())
+        : f1 >= 0 ? sum
+                  : "(__int128)s_pl";
+    jit_emit(s,
+             "      {\n"
+             "        __int128 p = %s;\n"
+             "        if (p != 0) {\n"
+             "          i128v pv = {(uint64_t)p,\n"
+             "                      (uint64_t)((unsigned __int128)p >> "
+             "64)};\n"
+             "          lds_acc_i128(facc[cell][%u], pv);\n"
+             "        }\n"
+             "      }\n",
+             expr.c_str(), (unsigned)a);
+  }
+  s += "    }\n"
+       "  }\n";
+}
+
+/* flush pass 4: the workgroup partials -> global cells */
+static void jit_v2_flush_partials(const dev_plan_hdr &ph, const jit_shape &,
+                                  const jit_strategy &st, std::string &s) {
+  const jit_v2_facc f = jit_v2_facc_of(ph, st);
+  if (f.any())
+    jit_emit(s,
              "  __syncthreads();\n"
              "  /* flush pass 4: one global accumulate per (cell, aggregate) "
              "*/\n"
@@ -1794,9 +1634,26 @@ static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
              "      gtable[ce].cells[a][1] = 1;\n"
              "    }\n"
              "  }\n",
-             f_sum, f_min | f_max, f_min);
-    s += b;
-  }
+             f.sum, f.min | f.max, f.min);
   s += "}\n";
+}
+
+static std::string jit_gen_source_v2(const dev_plan_hdr &ph,
+                                     const jit_shape &js,
+                                     const jit_strategy &st) {
+  std::string s;
+  jit_v2_prologue(ph, js, st, s);
+  jit_v2_lds(ph, js, st, s);
+  jit_v2_tables(ph, js, st, s);
+  if (st.bdesc) jit_v2_block_head_bdesc(ph, js, st, s);
+  else jit_v2_block_head_blocks(ph, js, st, s);
+  jit_v2_leaf_preambles(ph, js, st, s);
+  jit_v2_sweep(ph, js, st, s); /* holds jit_v2_accumulate */
+  jit_v2_flush_head(ph, js, st, s);
+  jit_v2_flush_cells(ph, js, st, s);    /* pass 1 */
+  jit_v2_flush_hists(ph, js, st, s);    /* pass 2 */
+  jit_v2_flush_joint(ph, js, st, s);    /* pass 3 */
+  jit_v2_flush_partials(ph, js, st, s); /* pass 4 */
   return s;
 }
+

@@ -9,100 +9,49 @@
  * column indices, scale constants, pass slots. Sums are exact int128,
  * accumulated per window as four 32-bit-digit sums (returnless LDS atomics,
  * reconstructed exactly at the window merge) and merged per block.
+ *
+ * jit_gen_source lists the kernel's phases: header, per-block preamble,
+ * sweep, merge. Each takes (plan, shape, strategy, out).
  */
 
-static void jit_emit_agg_program(std::string &s, const dev_plan_hdr &ph,
-                                 const jit_shape &js) {
-  char buf2[512];
-  auto reg_of = [&](uint8_t need_idx) -> int {
-    uint8_t col = ph.need_cols[need_idx];
-    for (int j = 0; j < js.n_vc; j++)
-      if (js.vcol[j] == col) return j;
-    return 0;
-  };
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    const dev_agg &g = ph.aggs[a];
-    if (js.agg_wa[a] == 0xFF) continue;
-    int wa = js.agg_wa[a];
-    switch (g.kind) {
-      case OBX_AGG_COUNT: /* COUNT(col) */
-        snprintf(buf2, sizeof buf2,
-                 "          if (!nu%d) atomicAdd(&wacc[%d][cell][0], 1ull);\n",
-                 reg_of(g.ia), wa);
-        s += buf2;
-        break;
-      case OBX_AGG_SUM:
-        snprintf(buf2, sizeof buf2,
-                 "          if (!nu%d && v%d)\n"
-                 "            ACC4(%d, i128_from_i64(v%d));\n",
-                 reg_of(g.ia), reg_of(g.ia), wa, reg_of(g.ia));
-        s += buf2;
-        break;
-      case OBX_AGG_SUM_PROD2: {
-        bool f2 = (js.agg_f2 >> a) & 1;
-        const dev_agg &g3 = f2 ? ph.aggs[a + 1] : g;
-        snprintf(buf2, sizeof buf2,
-                 "          if (!nu%d && !nu%d) {\n"
-                 "            i128v p2 = i128_mul_i64(v%d, %lldll - v%d);\n"
-                 "            if (p2.lo | p2.hi) ACC4(%d, p2);\n",
-                 reg_of(g.ia), reg_of(g.ib), reg_of(g.ia),
-                 (long long)g.one_b, reg_of(g.ib), wa);
-        s += buf2;
-        if (f2) {
-          snprintf(buf2, sizeof buf2,
-                   "            if (!nu%d) {\n"
-                   "              i128v p3 = i128_mul_pos_i64(p2, %lldll + "
-                   "v%d);\n"
-                   "              if (p3.lo | p3.hi) ACC4(%d, p3);\n"
-                   "            }\n",
-                   reg_of(g3.ic), (long long)g3.one_c, reg_of(g3.ic), wa + 1);
-          s += buf2;
-          a++;
-        }
-        s += "          }\n";
-        break;
-      }
-      case OBX_AGG_SUM_PROD3:
-        snprintf(buf2, sizeof buf2,
-                 "          if (!nu%d && !nu%d && !nu%d) {\n"
-                 "            i128v p3 = i128_mul_pos_i64(\n"
-                 "                i128_mul_i64(v%d, %lldll - v%d), %lldll + "
-                 "v%d);\n"
-                 "            if (p3.lo | p3.hi) ACC4(%d, p3);\n"
-                 "          }\n",
-                 reg_of(g.ia), reg_of(g.ib), reg_of(g.ic), reg_of(g.ia),
-                 (long long)g.one_b, reg_of(g.ib), (long long)g.one_c,
-                 reg_of(g.ic), wa);
-        s += buf2;
-        break;
-      case OBX_AGG_SUM_MUL:
-        snprintf(buf2, sizeof buf2,
-                 "          if (!nu%d && !nu%d) {\n"
-                 "            i128v p = i128_mul_i64(v%d, v%d);\n"
-                 "            if (p.lo | p.hi) ACC4(%d, p);\n"
-                 "          }\n",
-                 reg_of(g.ia), reg_of(g.ib), reg_of(g.ia), reg_of(g.ib), wa);
-        s += buf2;
-        break;
-      default:
-        break;
-    }
-  }
+/* all the v1 kernel takes beyond the plan: the waves-per-block floor. 7
+   WGs/CU measured best for the Q1/Q6 shapes (LDS ~22 KB, ~72 VGPRs);
+   OBX_JIT_WPB overrides for experiments (read by jit_scan_choose, pasted
+   as given) */
+struct jit_v1_strategy {
+  std::string wpb = "7";
+};
+
+static std::string jit_v1_sig(const jit_v1_strategy &st) {
+  return "V1|p" + st.wpb + "|";
 }
 
-static std::string jit_gen_source(const dev_plan_hdr &ph,
-                                  const jit_shape &js) {
+/* the null-pointer or named group dev_col argument of build_group_key */
+static const char *jit_v1_gd(int NG, int g) {
+  return NG > g ? (g ? "gd1" : "gd0") : "(const dev_col *)nullptr";
+}
+
+/* exact total of a window's four digit sums, into `tot` */
+static void jit_v1_emit_digits(std::string &s, int wa, const char *brk) {
+  jit_emit(s,
+           "        {\n"
+           "          uint64_t d0 = wacc[%1$d][cell][0], d1 = "
+           "wacc[%1$d][cell][1];\n"
+           "          uint64_t d2 = wacc[%1$d][cell][2], d3 = "
+           "wacc[%1$d][cell][3];\n"
+           "          unsigned __int128 tot =%2$s((unsigned __int128)d3 << 96) "
+           "+\n"
+           "              ((unsigned __int128)d2 << 64) +\n"
+           "              ((unsigned __int128)d1 << 32) + d0;\n",
+           wa, brk);
+}
+
+static void jit_v1_header(const dev_plan_hdr &ph, const jit_shape &js,
+                          const jit_v1_strategy &st, std::string &s) {
   const int NG = ph.n_group_cols;
-  const int NL = ph.n_leaves;
-  char b[1024];
-  std::string s;
   s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n\n";
-  /* waves-per-block floor for the specialized kernel: 7 WGs/CU measured
-     best for the Q1/Q6 shapes (LDS ~22 KB, ~72 VGPRs); OBX_JIT_WPB
-     overrides for experiments */
-  const char *wpb = getenv("OBX_JIT_WPB");
-  s += std::string("#define OBX_JIT_WPB ") + (wpb ? wpb : "7") + "\n";
-  snprintf(b, sizeof b,
+  jit_emit(s, "#define OBX_JIT_WPB %s\n", st.wpb.c_str());
+  jit_emit(s,
            "#define NL %d\n#define NG %d\n#define NWA %d\n"
            "#define ACC4(WA, PV)                                          \\\n"
            "  do {                                                        \\\n"
@@ -117,16 +66,13 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
            "      atomicAdd(&w_[3], (unsigned long long)(int64_t)(int32_t)( \\\n"
            "                            (PV).hi >> 32));                  \\\n"
            "  } while (0)\n\n",
-           NL, NG, js.n_wa > 0 ? js.n_wa : 1);
-  s += b;
-  snprintf(b, sizeof b,
+           (int)ph.n_leaves, NG, js.n_wa > 0 ? js.n_wa : 1);
+  jit_emit(s,
            "#define GD0P %s\n#define GD1P %s\n"
            "#define KL0V %u\n#define KL1V %u\n\n",
-           NG > 0 ? "gd0" : "(const dev_col *)nullptr",
-           NG > 1 ? "gd1" : "(const dev_col *)nullptr",
-           (unsigned)ph.group_len[0], (unsigned)ph.group_len[1]);
-  s += b;
-  snprintf(b, sizeof b,
+           jit_v1_gd(NG, 0), jit_v1_gd(NG, 1), (unsigned)ph.group_len[0],
+           (unsigned)ph.group_len[1]);
+  jit_emit(s,
            "/* right-sized LDS group table: the JIT kernel writes one\n"
            "   stripe and exactly n_aggs cells, cutting LDS for occupancy\n"
            "   (the generic lds_table is 16x8x2 cells) */\n"
@@ -154,7 +100,6 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
            "  return -1;\n"
            "}\n\n",
            (unsigned)ph.n_aggs);
-  s += b;
   s +=
       "extern \"C\" __global__ __launch_bounds__(256, OBX_JIT_WPB) void k_jit_scan(\n"
       "    const uint8_t *__restrict__ buf, const dev_block *__restrict__ "
@@ -177,7 +122,7 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
       "  for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {\n"
       "    tab.key[s] = OBX_KEY_EMPTY;\n"
       "    tab.count[s] = 0;\n";
-  snprintf(b, sizeof b,
+  jit_emit(s,
            "    for (uint32_t a = 0; a < %u; a++) {\n"
            "      tab.cell[s][a][0] = 0;\n"
            "      tab.cell[s][a][1] = 0;\n"
@@ -186,7 +131,15 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
            "  if (tid == 0) wg_passed = 0;\n"
            "  __syncthreads();\n\n",
            (unsigned)ph.n_aggs);
-  s += b;
+}
+
+/* block loop head: verdict, stage, the window loop, the filter (pass
+   bitmap for several leaves, inline context for one), group and value
+   contexts, window accumulator zero */
+static void jit_v1_block_preamble(const dev_plan_hdr &ph, const jit_shape &js,
+                                  const jit_v1_strategy &, std::string &s) {
+  const int NG = ph.n_group_cols;
+  const int NL = ph.n_leaves;
   s +=
       "  for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) "
       "{\n"
@@ -289,41 +242,99 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
     s += "      unsigned long long my_cnt = 0;\n";
   }
   /* group contexts + window accumulator zero */
-  if (NG > 0) {
-    snprintf(b, sizeof b,
-             "      const dev_col *gd0 = &cur.cols[%u];\n"
-             "      col_ctx g0 = make_col_ctx(*gd0, blk_bit);\n"
-             "      const uint32_t dim0 = g0.count + 1;\n",
-             (unsigned)ph.need_cols[ph.group_idx[0]]);
-    s += b;
-  }
-  if (NG > 1) {
-    snprintf(b, sizeof b,
-             "      const dev_col *gd1 = &cur.cols[%u];\n"
-             "      col_ctx g1 = make_col_ctx(*gd1, blk_bit);\n"
-             "      const uint32_t dim1 = g1.count + 1;\n",
-             (unsigned)ph.need_cols[ph.group_idx[1]]);
-    s += b;
-  }
+  for (int g = 0; g < NG; g++)
+    jit_emit(s,
+             "      const dev_col *gd%1$d = &cur.cols[%2$u];\n"
+             "      col_ctx g%1$d = make_col_ctx(*gd%1$d, blk_bit);\n"
+             "      const uint32_t dim%1$d = g%1$d.count + 1;\n",
+             g, (unsigned)ph.need_cols[ph.group_idx[g]]);
   s += NG == 0 ? "      const uint32_t n_cells = 1;\n"
       : NG == 1 ? "      const uint32_t n_cells = dim0;\n"
                 : "      const uint32_t n_cells = dim0 * dim1;\n";
-  snprintf(b, sizeof b,
-           "      for (uint32_t i = tid; i < NWA * 16 * 4; i += WG)\n"
-           "        (&wacc[0][0][0])[i] = 0;\n"
-           "      for (uint32_t i = tid; i < 16; i += WG) wcnt[i] = 0;\n"
-           "      if (tid == 0) spill_cnt = 0;\n"
-           "      __syncthreads();\n");
-  s += b;
+  s += "      for (uint32_t i = tid; i < NWA * 16 * 4; i += WG)\n"
+       "        (&wacc[0][0][0])[i] = 0;\n"
+       "      for (uint32_t i = tid; i < 16; i += WG) wcnt[i] = 0;\n"
+       "      if (tid == 0) spill_cnt = 0;\n"
+       "      __syncthreads();\n";
   /* value-column contexts (registers: the specialized kernel carries no
      plan machinery, so the uniform budget allows it) */
-  for (int j = 0; j < js.n_vc; j++) {
-    snprintf(b, sizeof b,
+  for (int j = 0; j < js.n_vc; j++)
+    jit_emit(s,
              "      const col_ctx c%d = make_col_ctx(cur.cols[%u], "
              "blk_bit);\n",
              j, (unsigned)js.vcol[j]);
-    s += b;
+}
+
+/* the aggregate program over one live row's decoded values */
+static void jit_v1_agg_program(const dev_plan_hdr &ph, const jit_shape &js,
+                               const jit_v1_strategy &, std::string &s) {
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    const dev_agg &g = ph.aggs[a];
+    if (js.agg_wa[a] == 0xFF) continue;
+    const int wa = js.agg_wa[a];
+    const int ja = js.slot(ph, g.ia), jb = js.slot(ph, g.ib),
+              jc = js.slot(ph, g.ic);
+    switch (g.kind) {
+      case OBX_AGG_COUNT: /* COUNT(col) */
+        jit_emit(s,
+                 "          if (!nu%d) atomicAdd(&wacc[%d][cell][0], 1ull);\n",
+                 ja, wa);
+        break;
+      case OBX_AGG_SUM:
+        jit_emit(s,
+                 "          if (!nu%1$d && v%1$d)\n"
+                 "            ACC4(%2$d, i128_from_i64(v%1$d));\n",
+                 ja, wa);
+        break;
+      case OBX_AGG_SUM_PROD2: {
+        jit_emit(s,
+                 "          if (!nu%1$d && !nu%2$d) {\n"
+                 "            i128v p2 = i128_mul_i64(v%1$d, %3$lldll - "
+                 "v%2$d);\n"
+                 "            if (p2.lo | p2.hi) ACC4(%4$d, p2);\n",
+                 ja, jb, (long long)g.one_b, wa);
+        if ((js.agg_f2 >> a) & 1) {
+          const dev_agg &g3 = ph.aggs[a + 1];
+          jit_emit(s,
+                   "            if (!nu%1$d) {\n"
+                   "              i128v p3 = i128_mul_pos_i64(p2, %2$lldll + "
+                   "v%1$d);\n"
+                   "              if (p3.lo | p3.hi) ACC4(%3$d, p3);\n"
+                   "            }\n",
+                   js.slot(ph, g3.ic), (long long)g3.one_c, wa + 1);
+          a++;
+        }
+        s += "          }\n";
+        break;
+      }
+      case OBX_AGG_SUM_PROD3:
+        jit_emit(s,
+                 "          if (!nu%1$d && !nu%2$d && !nu%3$d) {\n"
+                 "            i128v p3 = i128_mul_pos_i64(\n"
+                 "                i128_mul_i64(v%1$d, %4$lldll - v%2$d), "
+                 "%5$lldll + v%3$d);\n"
+                 "            if (p3.lo | p3.hi) ACC4(%6$d, p3);\n"
+                 "          }\n",
+                 ja, jb, jc, (long long)g.one_b, (long long)g.one_c, wa);
+        break;
+      case OBX_AGG_SUM_MUL:
+        jit_emit(s,
+                 "          if (!nu%1$d && !nu%2$d) {\n"
+                 "            i128v p = i128_mul_i64(v%1$d, v%2$d);\n"
+                 "            if (p.lo | p.hi) ACC4(%3$d, p);\n"
+                 "          }\n",
+                 ja, jb, wa);
+        break;
+      default:
+        break;
+    }
   }
+}
+
+static void jit_v1_sweep(const dev_plan_hdr &ph, const jit_shape &js,
+                         const jit_v1_strategy &st, std::string &s) {
+  const int NG = ph.n_group_cols;
+  const int NL = ph.n_leaves;
   s += "\n"
        "      for (uint32_t it = 0; it < iters; it++) {\n"
        "        uint32_t rr = it * WG + tid;\n";
@@ -349,51 +360,50 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
          "          if (lane == 0) my_cnt += __popcll(pm);\n"
          "        }\n";
   }
-  if (NG > 0)
-    s += "        uint32_t ref0 = (uint32_t)bit_read_at(\n"
-         "            bv.base, bv.rbase_bit + (uint32_t)(gd0->data_bit - "
-         "blk_bit) +\n"
-         "                         (uint64_t)r * g0.W, g0.W);\n"
-         "        if (ref0 > g0.count) ref0 = g0.count;\n"
-         "        uint32_t cell = ref0;\n";
-  if (NG > 1)
-    s += "        uint32_t ref1 = (uint32_t)bit_read_at(\n"
-         "            bv.base, bv.rbase_bit + (uint32_t)(gd1->data_bit - "
-         "blk_bit) +\n"
-         "                         (uint64_t)r * g1.W, g1.W);\n"
-         "        if (ref1 > g1.count) ref1 = g1.count;\n"
-         "        cell += ref1 * dim0;\n";
+  for (int g = 0; g < NG; g++) {
+    jit_emit(s,
+             "        uint32_t ref%1$d = (uint32_t)bit_read_at(\n"
+             "            bv.base, bv.rbase_bit + (uint32_t)(gd%1$d->data_bit - "
+             "blk_bit) +\n"
+             "                         (uint64_t)r * g%1$d.W, g%1$d.W);\n"
+             "        if (ref%1$d > g%1$d.count) ref%1$d = g%1$d.count;\n",
+             g);
+    s += g ? "        cell += ref1 * dim0;\n" : "        uint32_t cell = ref0;\n";
+  }
   if (NG == 0) s += "        const uint32_t cell = 0;\n";
   s += "        if (live) {\n"
        "          rep_row[cell] = r;\n"
        "          atomicAdd(&wcnt[cell], 1ull);\n"
        "        }\n";
-  for (int j = 0; j < js.n_vc; j++) {
-    snprintf(b, sizeof b,
-             "        bool nu%d;\n"
-             "        int64_t v%d = ctx_value(bv, c%d, r, nu%d);\n",
-             j, j, j, j);
-    s += b;
-  }
+  for (int j = 0; j < js.n_vc; j++)
+    jit_emit(s,
+             "        bool nu%1$d;\n"
+             "        int64_t v%1$d = ctx_value(bv, c%1$d, r, nu%1$d);\n",
+             j);
   s += "        if (live) {\n";
-  jit_emit_agg_program(s, ph, js);
+  jit_v1_agg_program(ph, js, st, s);
   s += "        }\n"
        "      }\n";
   if (NL <= 1)
     s += "      if (lane == 0 && my_cnt) atomicAdd(&wg_passed, my_cnt);\n";
+}
+
+/* window merge into the workgroup's LDS table (full table: spill to the
+   global one), then the LDS table's flush at the end of the kernel */
+static void jit_v1_merge(const dev_plan_hdr &ph, const jit_shape &js,
+                         const jit_v1_strategy &, std::string &s) {
+  const int NG = ph.n_group_cols;
   s += "      __syncthreads();\n"
        "\n"
        "      /* merge the window accumulators into the group table */\n"
        "      for (uint32_t cell = tid; cell < n_cells; cell += WG) {\n"
        "        unsigned long long cnt2 = wcnt[cell];\n"
        "        if (!cnt2) continue;\n";
-  snprintf(b, sizeof b,
+  jit_emit(s,
            "        uint64_t key = build_group_key(bv, NG, %s, %s, %u, %u,\n"
            "                                       rep_row[cell]);\n",
-           NG > 0 ? "gd0" : "(const dev_col *)nullptr",
-           NG > 1 ? "gd1" : "(const dev_col *)nullptr",
-           (unsigned)ph.group_len[0], (unsigned)ph.group_len[1]);
-  s += b;
+           jit_v1_gd(NG, 0), jit_v1_gd(NG, 1), (unsigned)ph.group_len[0],
+           (unsigned)ph.group_len[1]);
   s += "        int s2 = jit_slot(&tab, key);\n"
        "        if (s2 < 0) {\n"
        "          /* WG-local table full: queue the cell for the cold\n"
@@ -406,25 +416,15 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
        "        atomicAdd(&tab.count[s2], cnt2);\n";
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     if (js.agg_wa[a] == 0xFF) continue;
-    snprintf(b, sizeof b,
-             "        {\n"
-             "          uint64_t d0 = wacc[%d][cell][0], d1 = "
-             "wacc[%d][cell][1];\n"
-             "          uint64_t d2 = wacc[%d][cell][2], d3 = "
-             "wacc[%d][cell][3];\n"
-             "          unsigned __int128 tot =\n"
-             "              ((unsigned __int128)d3 << 96) +\n"
-             "              ((unsigned __int128)d2 << 64) +\n"
-             "              ((unsigned __int128)d1 << 32) + d0;\n"
+    jit_v1_emit_digits(s, js.agg_wa[a], "\n              ");
+    jit_emit(s,
              "          if (tot) {\n"
              "            i128v pv = {(uint64_t)tot, (uint64_t)(tot >> "
              "64)};\n"
              "            lds_acc_i128(tab.cell[s2][%u], pv);\n"
              "          }\n"
              "        }\n",
-             js.agg_wa[a], js.agg_wa[a], js.agg_wa[a], js.agg_wa[a],
              (unsigned)a);
-    s += b;
   }
   s += "      }\n"
        "      __syncthreads(); /* spill list ready */\n"
@@ -448,31 +448,20 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
        "        }\n"
        "        if (!found) { atomicAdd(&counters[1], cnt2); continue; }\n"
        "        atomicAdd(&gtable[gidx].count, cnt2);\n";
-  for (uint32_t a2 = 0; a2 < ph.n_aggs; a2++) {
-    if (js.agg_wa[a2] == 0xFF) {
-      snprintf(b, sizeof b,
-               "        g_acc_i128(gtable[gidx].cells[%u], cnt2, 0);\n",
-               (unsigned)a2);
-    } else {
-      snprintf(b, sizeof b,
-               "        {\n"
-               "          uint64_t d0 = wacc[%d][cell][0], d1 = "
-               "wacc[%d][cell][1];\n"
-               "          uint64_t d2 = wacc[%d][cell][2], d3 = "
-               "wacc[%d][cell][3];\n"
-               "          unsigned __int128 tot = ((unsigned __int128)d3 "
-               "<< 96) +\n"
-               "              ((unsigned __int128)d2 << 64) +\n"
-               "              ((unsigned __int128)d1 << 32) + d0;\n"
-               "          if (tot)\n"
-               "            g_acc_i128(gtable[gidx].cells[%u], "
-               "(uint64_t)tot,\n"
-               "                       (uint64_t)(tot >> 64));\n"
-               "        }\n",
-               js.agg_wa[a2], js.agg_wa[a2], js.agg_wa[a2], js.agg_wa[a2],
-               (unsigned)a2);
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (js.agg_wa[a] == 0xFF) {
+      jit_emit(s, "        g_acc_i128(gtable[gidx].cells[%u], cnt2, 0);\n",
+               (unsigned)a);
+      continue;
     }
-    s += b;
+    jit_v1_emit_digits(s, js.agg_wa[a], " ");
+    jit_emit(s,
+             "          if (tot)\n"
+             "            g_acc_i128(gtable[gidx].cells[%u], "
+             "(uint64_t)tot,\n"
+             "                       (uint64_t)(tot >> 64));\n"
+             "        }\n",
+             (unsigned)a);
   }
   s += "      }\n"
        "      __syncthreads(); /* pass_bm / accumulator reuse */\n"
@@ -499,21 +488,28 @@ static std::string jit_gen_source(const dev_plan_hdr &ph,
        "    unsigned long long cnt = tab.count[s];\n"
        "    atomicAdd(&gtable[idx].count, cnt);\n";
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (js.agg_wa[a] == 0xFF) {
-      snprintf(b, sizeof b,
+    if (js.agg_wa[a] == 0xFF)
+      jit_emit(s,
                "    g_acc_i128(gtable[idx].cells[%u], cnt, 0); /* COUNT(*) "
                "*/\n",
                (unsigned)a);
-    } else {
-      snprintf(b, sizeof b,
-               "    g_acc_i128(gtable[idx].cells[%u], tab.cell[s][%u][0],\n"
-               "               tab.cell[s][%u][1]);\n",
-               (unsigned)a, (unsigned)a, (unsigned)a);
-    }
-    s += b;
+    else
+      jit_emit(s,
+               "    g_acc_i128(gtable[idx].cells[%1$u], tab.cell[s][%1$u][0],\n"
+               "               tab.cell[s][%1$u][1]);\n",
+               (unsigned)a);
   }
   s += "  }\n"
        "}\n";
+}
+
+static std::string jit_gen_source(const dev_plan_hdr &ph, const jit_shape &js,
+                                  const jit_v1_strategy &st) {
+  std::string s;
+  jit_v1_header(ph, js, st, s);
+  jit_v1_block_preamble(ph, js, st, s);
+  jit_v1_sweep(ph, js, st, s);
+  jit_v1_merge(ph, js, st, s);
   return s;
 }
 
@@ -521,24 +517,18 @@ static std::string jit_plan_sig(const dev_plan_hdr &ph) {
   /* everything the generated SOURCE depends on (operand VALUES live in the
      uploaded leaf/bleaf arrays, so they are not part of the key) */
   std::string k;
-  char b[64];
-  snprintf(b, sizeof b, "L%dG%dA%d|", ph.n_leaves, ph.n_group_cols,
-           ph.n_aggs);
-  k += b;
-  for (uint32_t g = 0; g < ph.n_group_cols; g++) {
-    snprintf(b, sizeof b, "g%u:%u:%u|", g,
-             (unsigned)ph.need_cols[ph.group_idx[g]],
+  jit_emit(k, "L%dG%dA%d|", (int)ph.n_leaves, (int)ph.n_group_cols,
+           (int)ph.n_aggs);
+  for (uint32_t g = 0; g < ph.n_group_cols; g++)
+    jit_emit(k, "g%u:%u:%u|", g, (unsigned)ph.need_cols[ph.group_idx[g]],
              (unsigned)ph.group_len[g]);
-    k += b;
-  }
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     const dev_agg &g = ph.aggs[a];
-    snprintf(b, sizeof b, "a%u:%u:%u:%u:%u:%lld:%lld|", a, (unsigned)g.kind,
+    jit_emit(k, "a%u:%u:%u:%u:%u:%lld:%lld|", a, (unsigned)g.kind,
              (unsigned)(g.ia == 0xFF ? 255 : ph.need_cols[g.ia]),
              (unsigned)(g.ib == 0xFF ? 255 : ph.need_cols[g.ib]),
              (unsigned)(g.ic == 0xFF ? 255 : ph.need_cols[g.ic]),
              (long long)g.one_b, (long long)g.one_c);
-    k += b;
   }
   return k;
 }
