@@ -175,6 +175,18 @@ typedef struct dev_agg {
   int64_t one_b, one_c; /* 10^scale constants for PROD2/PROD3 */
 } dev_agg;
 
+/* aggs[a] is a SUM_PROD2 (kind 4) directly followed by a SUM_PROD3 (kind 5)
+ * over the same a and b: the two run as one pass, the PROD3 term being the
+ * PROD2 term times (one_c + c). */
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+__host__ __device__
+#endif
+static inline int obx_fuse_p3(const dev_agg *aggs, uint32_t n_aggs,
+                              uint32_t a) {
+  return aggs[a].kind == 4 && a + 1 < n_aggs && aggs[a + 1].kind == 5 &&
+         aggs[a + 1].ia == aggs[a].ia && aggs[a + 1].ib == aggs[a].ib;
+}
+
 #define OBX_DEV_MAX_NEED 12
 
 /* Packed per-block descriptor of the persistent scan JIT: everything that

@@ -18,9 +18,6 @@
 
 #define WG 256
 #define WAVES (WG / 64)
-#ifndef OBX_PIPELINE
-#define OBX_PIPELINE 0   /* 0 = single-buffer staging (higher occupancy; measured faster), 1 = double-buffered prefetch */
-#endif
 
 /* view of a block's bytes: either the global buffer (bias 0) or the LDS
  * staging copy (bias = block_byte * 8). All dev_col offsets are absolute;

@@ -1290,9 +1290,7 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     for (uint32_t a = 0; a < ph.n_aggs;) {
       const dev_agg &ag = ph.aggs[a];
       if (ag.kind == OBX_AGG_COUNT && ag.ia == 0xFF) { a++; continue; }
-      bool fuse = (ag.kind == OBX_AGG_SUM_PROD2 && a + 1 < ph.n_aggs &&
-                   ph.aggs[a + 1].kind == OBX_AGG_SUM_PROD3 &&
-                   ph.aggs[a + 1].ia == ag.ia && ph.aggs[a + 1].ib == ag.ib);
+      const bool fuse = obx_fuse_p3(ph.aggs, ph.n_aggs, a);
       hipLaunchKernelGGL(k_agg_pass, dim3(grid_for(h.n_blocks)),
                          dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
                          h.d_blocks, h.n_blocks, ph, a, h.d_bitmap,

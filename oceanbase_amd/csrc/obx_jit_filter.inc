@@ -279,7 +279,7 @@ static void jit_f_direct_tests(const dev_plan_hdr &ph,
 
 static void jit_f_prologue(const dev_plan_hdr &ph, const jit_fstrategy &st,
                            std::string &s) {
-  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
+  s += "#include \"obx_dev_common.h\"\n"
        "#include \"obx_jit_dev.h\"\n\n";
   jit_emit(s,
            "#define NL %d\n#define FSL %d\n#define FR %d\n"

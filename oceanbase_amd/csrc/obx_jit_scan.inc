@@ -808,7 +808,7 @@ static jit_v2_facc jit_v2_facc_of(const dev_plan_hdr &ph,
 
 static void jit_v2_prologue(const dev_plan_hdr &ph, const jit_shape &,
                             const jit_strategy &st, std::string &s) {
-  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n"
+  s += "#include \"obx_dev_common.h\"\n"
        "#include \"obx_jit_dev.h\"\n\n";
   jit_emit(s,
            "#define NL %d\n#define NG %d\n#define NW64 %d\n"

@@ -49,7 +49,7 @@ static void jit_v1_emit_digits(std::string &s, int wa, const char *brk) {
 static void jit_v1_header(const dev_plan_hdr &ph, const jit_shape &js,
                           const jit_v1_strategy &st, std::string &s) {
   const int NG = ph.n_group_cols;
-  s += "#define OBX_PIPELINE 0\n#include \"obx_dev_common.h\"\n\n";
+  s += "#include \"obx_dev_common.h\"\n\n";
   jit_emit(s, "#define OBX_JIT_WPB %s\n", st.wpb.c_str());
   jit_emit(s,
            "#define NL %d\n#define NG %d\n#define NWA %d\n"

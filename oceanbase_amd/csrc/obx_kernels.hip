@@ -25,8 +25,30 @@
  *    (ob_exec_hash_struct_vec.h:1718, share/aggregate/sum.h) with exact
  *    integer arithmetic.
  *  - no MFMA anywhere: this path is memory-bound integer work.
+ *
+ * These are the GENERIC kernels: what every plan the JIT does not specialise
+ * runs (MIN/MAX without a v2 strategy, OR programs, slow encodings, more
+ * than 4 value columns, OBX_JIT=0, the growth path, the OBX_PIPELINE_AGG
+ * kernel DAG) plus the get_rows decode kernels. Each step exists once and
+ * the kernels are assembled from the steps:
+ *   blk_open<STAGE>      open a block, staged or not      (obx_blk.h)
+ *   filter_window<PROG>  phase 1: a row window -> LDS pass bitmap
+ *   group_open/group_row a surviving row -> group-table slot; the table's
+ *                        find-or-insert and the row-count sink are arguments
+ *   opnd_open/opnd_value an aggregate operand: ctx fast path or col_value2
+ *   agg_term / agg_row   a kind's term and null rule, into an lds_sink or a
+ *                        gcell_sink
+ *   flush_cells<NST>     LDS cell stripes -> global cell
+ *   gtable_slot<SHIFT>   global table find-or-insert
+ *   store_datum          one VEC_FIXED datum                (obx_blk.h)
+ * scan_filter_agg_body = open + filter_window + group_row(lds_slot) +
+ * agg_row(lds_sink) + flush_cells; filter_body = open + filter_window +
+ * bitmap / row-id output; k_group_pass = open + group_row(gtable_slot);
+ * k_agg_pass = open + agg_row(lds_sink) + flush_cells; k_scan_agg_direct =
+ * open + gtable_slot + agg_term(gcell_sink); the decode kernels = open +
+ * decode_rows.
  */
-#include "obx_dev_common.h"
+#include "obx_blk.h"
 
 struct prog_spec { uint8_t n; uint8_t t[15]; };
 
@@ -88,7 +110,301 @@ __device__ __forceinline__ void filter_prog_phase(
   __syncthreads();
 }
 
+/* every in-range row of the window passes */
+__device__ __forceinline__ void pass_all(uint64_t *pass_bm, uint32_t rows) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t iters = (rows + WG - 1) / WG;
+  for (uint32_t it = 0; it < iters; it++) {
+    uint32_t rr = it * WG + tid;
+    uint64_t m = __ballot(rr < rows);
+    if (lane == 0) pass_bm[it * WAVES + wv] = m;
+  }
+}
 
+/* ---- phase 1 of both scan bodies: filter one row window [w0, w0 + rows)
+   into the LDS pass bitmap, one leaf at a time (the reference's per-leaf
+   bitmap combine, ob_pushdown_filter.cpp:1559; a single live leaf context
+   keeps uniform state inside the SGPR budget). AND-only plans fold
+   progressively; plans with a combine program evaluate per-leaf bitmaps
+   (leaf_bm) then a word-wise postfix pass. blk_verdict is the block's
+   fold_prog3 class: 1 = every row passes. ---- */
+template <bool PROG>
+__device__ __forceinline__ void filter_window(
+    const blk_view &bv, const dev_block &cur,
+    const dev_leaf *__restrict__ plan_leaves, const blk_leaf *bl,
+    const dev_plan_hdr &ph, uint8_t blk_verdict, uint64_t blk_bit,
+    uint32_t rows, uint32_t w0, uint64_t *pass_bm, uint64_t *leaf_bm) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t iters = (rows + WG - 1) / WG;
+  if (blk_verdict == 1) {
+    pass_all(pass_bm, rows);
+  } else if constexpr (!PROG) {
+    bool first = true;
+    for (uint32_t i = 0; i < ph.n_leaves; i++) {
+      const blk_leaf lfb = bl[i];
+      if (lfb.mode == OBX_LEAF_ALL &&
+          !(cur.cols[plan_leaves[i].col].flags & OBX_DF_HAS_EXT))
+        continue; /* every row passes this leaf */
+      leaf_ctx lc = make_leaf_ctx(cur, plan_leaves[i], bl[i], blk_bit);
+      const bool slow = lc.slow;
+      for (uint32_t it = 0; it < iters; it++) {
+        uint64_t prev = first ? ~0ull : pass_bm[it * WAVES + wv];
+        if (!prev) { if (first && lane == 0) pass_bm[it * WAVES + wv] = 0;
+                     continue; }
+        uint32_t rr = it * WG + tid;
+        uint32_t r = w0 + rr;
+        bool pass = rr < rows && ((prev >> lane) & 1);
+        if (pass)
+          pass = slow ? leaf_match(bv, cur, plan_leaves[i], bl[i], r)
+                      : leaf_ctx_match(bv, lc, plan_leaves[i], r);
+        uint64_t m = __ballot(pass);
+        if (lane == 0) pass_bm[it * WAVES + wv] = m;
+      }
+      first = false;
+    }
+    if (first) pass_all(pass_bm, rows); /* no live leaves */
+  } else {
+    prog_spec ps;
+    ps.n = ph.n_prog;
+    for (int p = 0; p < 15; p++) ps.t[p] = ph.prog[p];
+    filter_prog_phase(bv, cur, plan_leaves, bl, ph.n_leaves, ps, rows, w0,
+                      blk_bit, (lds3_u64 *)pass_bm, (lds3_u64 *)leaf_bm);
+  }
+}
+
+/* ---- grouping: a surviving row -> its slot in a group table.
+   Fast path (the reference's storage group-by pushdown design,
+   ob_pushdown_aggregate_vec.h:445 / read_reference): when every group
+   column is dict-encoded and the ref product is small, rows map to cells
+   by packed REFS alone; cell -> slot resolves lazily, once per block, via
+   the dict values (cell_slot, 254 = not resolved yet). NULL group values
+   set flag bits in the top key byte (data bytes stay zero). ---- */
+struct group_ctx {
+  col_ctx g0, g1;
+  const dev_col *gd0, *gd1;
+  uint32_t dim0;
+  bool ref_fast;
+};
+
+__device__ __forceinline__ group_ctx group_open(const dev_plan_hdr &ph,
+                                                const dev_block &cur,
+                                                uint64_t blk_bit) {
+  group_ctx g;
+  g.gd0 = g.gd1 = nullptr;
+  if (ph.n_group_cols > 0) {
+    g.gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
+    g.g0 = make_col_ctx(*g.gd0, blk_bit);
+  }
+  if (ph.n_group_cols > 1) {
+    g.gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
+    g.g1 = make_col_ctx(*g.gd1, blk_bit);
+  }
+  g.dim0 = (ph.n_group_cols > 0) ? g.g0.count + 1 : 1;
+  const uint32_t dim1 = (ph.n_group_cols > 1) ? g.g1.count + 1 : 1;
+  g.ref_fast = ph.n_group_cols > 0 && g.g0.kind == 1 &&
+               (ph.n_group_cols < 2 || g.g1.kind == 1) &&
+               g.dim0 * dim1 <= 64;
+  return g;
+}
+
+/* Slot of surviving row r, 255 = none. find(key) is the table's
+   find-or-insert (a slot, or < 0 when full; slots past 254 do not fit the
+   u8 map either): a row without a slot counts into counters[1]. count(slot)
+   takes the row into the slot's row count. */
+template <class FIND, class COUNT>
+__device__ __forceinline__ uint8_t group_row(
+    const blk_view &bv, const dev_plan_hdr &ph, const group_ctx &g,
+    uint8_t *cell_slot, uint32_t r, unsigned long long *counters, FIND find,
+    COUNT count) {
+  uint32_t cell = 0;
+  uint8_t cs = 254;
+  if (g.ref_fast) {
+    cell = (uint32_t)bit_read_at(
+        bv.base, bv.rbase_bit + g.g0.data_bit + (uint64_t)r * g.g0.W, g.g0.W);
+    if (cell > g.g0.count) cell = g.g0.count; /* nope -> null bucket */
+    if (ph.n_group_cols > 1) {
+      uint32_t ref1 = (uint32_t)bit_read_at(
+          bv.base, bv.rbase_bit + g.g1.data_bit + (uint64_t)r * g.g1.W,
+          g.g1.W);
+      if (ref1 > g.g1.count) ref1 = g.g1.count;
+      cell += ref1 * g.dim0;
+    }
+    cs = cell_slot[cell];
+  }
+  if (cs == 254) {
+    int s = find(build_group_key(bv, ph.n_group_cols, g.gd0, g.gd1,
+                                 ph.group_len[0], ph.group_len[1], r));
+    cs = (s < 0 || s >= 255) ? 255 : (uint8_t)s;
+    if (cs == 255) atomicAdd(&counters[1], 1ull);
+    if (g.ref_fast) cell_slot[cell] = cs;
+  }
+  if (cs != 255) count(cs);
+  return cs;
+}
+
+/* ---- aggregates: one row's contribution to one aggregate (or to a
+   SUM_PROD2 and the SUM_PROD3 fused with it, obx_fuse_p3). ---- */
+struct agg_opnd {
+  col_ctx cx;
+  const dev_col *dc; /* nullptr: the aggregate has no such operand */
+};
+
+__device__ __forceinline__ agg_opnd opnd_open(const dev_plan_hdr &ph,
+                                              const dev_block &cur,
+                                              uint8_t idx, uint64_t blk_bit) {
+  agg_opnd o;
+  o.dc = nullptr;
+  if (idx != 0xFF) {
+    o.dc = &cur.cols[ph.need_cols[idx]];
+    o.cx = make_col_ctx(*o.dc, blk_bit);
+  }
+  return o;
+}
+
+/* ctx fast path, or the full decoder for a slow encoding */
+__device__ __forceinline__ int64_t opnd_value(const blk_view &bv,
+                                              const dev_block &cur,
+                                              const agg_opnd &o, uint32_t r,
+                                              bool &isn) {
+  return (o.cx.kind == 4) ? col_value2(bv, cur, *o.dc, r, isn)
+                          : ctx_value(bv, o.cx, r, isn);
+}
+
+/* where a term goes: a lane stripe of an LDS cell (c1: the fused mate's),
+   or a 256-bit cell of the global table (the mate's is the next one) */
+struct lds_sink {
+  unsigned long long *c0, *c1;
+  __device__ __forceinline__ void count() const { atomicAdd(&c0[0], 1ull); }
+  __device__ __forceinline__ void add(i128v v) const { lds_acc_i128(c0, v); }
+  __device__ __forceinline__ void add_mate(i128v v) const {
+    lds_acc_i128(c1, v);
+  }
+  __device__ __forceinline__ void minmax(int64_t v, bool is_min) const {
+    cas_minmax(&c0[0], v, is_min);
+    c0[1] = 1;
+  }
+};
+
+struct gcell_sink {
+  unsigned long long *c0;
+  __device__ __forceinline__ void count() const { g_acc_i128(c0, 1ull, 0ull); }
+  __device__ __forceinline__ void add(i128v v) const {
+    g_acc_i128(c0, v.lo, v.hi);
+  }
+  __device__ __forceinline__ void add_mate(i128v v) const {
+    g_acc_i128(c0 + 4, v.lo, v.hi);
+  }
+  __device__ __forceinline__ void minmax(int64_t v, bool is_min) const {
+    cas_minmax(&c0[0], v, is_min);
+    c0[1] = 1;
+  }
+};
+
+/* the term of kind `kind` and its null rule: a NULL operand drops the term
+   (a NULL c drops only the PROD3 half of a fused pair) */
+template <class SINK>
+__device__ __forceinline__ void agg_term(uint32_t kind, bool fuse_p3,
+                                         int64_t one_b, int64_t one_c,
+                                         int64_t va, bool na, int64_t vb,
+                                         bool nb, int64_t vc, bool nc,
+                                         const SINK sink) {
+  switch (kind) {
+    case 0: /* COUNT(col) */
+      if (!na) sink.count();
+      break;
+    case 1: /* SUM */
+      if (!na) sink.add(i128_from_i64(va));
+      break;
+    case 2: case 3: /* MIN / MAX */
+      if (!na) sink.minmax(va, kind == 2);
+      break;
+    case 4: /* SUM_PROD2 (+ fused PROD3 mate) */
+      if (!na && !nb) {
+        i128v p2 = i128_mul_i64(va, one_b - vb);
+        sink.add(p2);
+        if (fuse_p3 && !nc) sink.add_mate(i128_mul_pos_i64(p2, one_c + vc));
+      }
+      break;
+    case 5: /* SUM_PROD3 standalone */
+      if (!na && !nb && !nc)
+        sink.add(i128_mul_pos_i64(i128_mul_i64(va, one_b - vb), one_c + vc));
+      break;
+    case 6: /* SUM_MUL */
+      if (!na && !nb) sink.add(i128_mul_i64(va, vb));
+      break;
+    default: break;
+  }
+}
+
+/* fetch the operands the kind reads, then its term. ag2 is the fused mate
+   (ag itself when not fused). */
+template <class SINK>
+__device__ __forceinline__ void agg_row(
+    const blk_view &bv, const dev_block &cur, uint32_t kind, bool fuse_p3,
+    const dev_agg &ag, const dev_agg &ag2, const agg_opnd &oa,
+    const agg_opnd &ob, const agg_opnd &oc, uint32_t r, const SINK sink) {
+  bool na = false, nb = false, nc = false;
+  int64_t va = 0, vb = 0, vc = 0;
+  if (oa.dc) va = opnd_value(bv, cur, oa, r, na);
+  if (kind >= 4 && ob.dc) vb = opnd_value(bv, cur, ob, r, nb);
+  if ((kind == 5 || fuse_p3) && oc.dc) vc = opnd_value(bv, cur, oc, r, nc);
+  agg_term(kind, fuse_p3, ag.one_b, ag2.one_c, va, na, vb, nb, vc, nc, sink);
+}
+
+/* merge the NST lane stripes of one aggregate's LDS cell into its global
+   cell: min/max per stripe that saw a value, sums as one 256-bit add */
+template <uint32_t NST>
+__device__ __forceinline__ void flush_cells(
+    const unsigned long long (*st)[2], uint8_t kind,
+    unsigned long long *gcell) {
+  if (kind == 2 || kind == 3) {
+    for (uint32_t s = 0; s < NST; s++) {
+      if (st[s][1]) {
+        cas_minmax(&gcell[0], (int64_t)st[s][0], kind == 2);
+        gcell[1] = 1;
+      }
+    }
+  } else {
+    uint64_t lo = 0, hi = 0;
+    for (uint32_t s = 0; s < NST; s++) {
+      uint64_t l = st[s][0];
+      uint64_t nlo = lo + l;
+      hi += st[s][1] + (nlo < l);
+      lo = nlo;
+    }
+    if (lo | hi) g_acc_i128(gcell, lo, hi);
+  }
+}
+
+/* ---- global group table (open addressing over 1 << SHIFT gslots) ---- */
+template <uint32_t SHIFT>
+__device__ __forceinline__ uint32_t gtable_home(uint64_t key) {
+  return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - SHIFT)) &
+         ((1u << SHIFT) - 1);
+}
+
+/* find-or-insert a key; returns its slot, or -1 when the table is full */
+template <uint32_t SHIFT>
+__device__ __forceinline__ int gtable_slot(gslot *gt, uint64_t key) {
+  uint32_t idx = gtable_home<SHIFT>(key);
+  for (uint32_t probe = 0; probe < (1u << SHIFT); probe++) {
+    unsigned long long k = __hip_atomic_load(
+        &gt[idx].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == key) return (int)idx;
+    if (k == OBX_KEY_EMPTY) {
+      unsigned long long c = atomicCAS(&gt[idx].key, OBX_KEY_EMPTY,
+                                       (unsigned long long)key);
+      if (c == OBX_KEY_EMPTY || c == key) return (int)idx;
+    }
+    idx = (idx + 1) & ((1u << SHIFT) - 1);
+  }
+  return -1;
+}
+
+/* compile-time tag: hands a constant to a generic lambda */
+template <int V> struct kc { static constexpr int v = V; };
+
+/* ---------------- fused scan->filter->aggregate kernel ------------------ */
 template <bool STAGE, bool PROG>
 __device__ void scan_filter_agg_body(
     const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
@@ -110,7 +426,7 @@ __device__ void scan_filter_agg_body(
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63;
   const uint32_t wv = tid >> 6;
-
+  const uint32_t stripe = lane & (OBX_STRIPES - 1);
 
   for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
     tab.key[s] = OBX_KEY_EMPTY;
@@ -128,98 +444,26 @@ __device__ void scan_filter_agg_body(
   if (tid == 0) wg_passed = 0;
   __syncthreads();
 
-  uint32_t par = 0;
-  if (STAGE && OBX_PIPELINE && blockIdx.x < n_blocks)
-    stage_issue(buf, blocks[blockIdx.x], lds_blk);
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
     const dev_block &cur = blocks[b];
+    const blk_leaf *bl = bleaves + (uint64_t)b * ph.n_leaves;
     /* constant-result short-circuit: fold the combine program over the
        lowered leaf classes — a FALSE block is skipped before staging (cf.
        the reference's filter constant results / skip-index pruning) */
-    uint8_t blk_verdict = 2;
-    if (!OBX_PIPELINE || !STAGE) {
-      blk_verdict = fold_prog3(ph, cur, plan_leaves,
-                               bleaves + (uint64_t)b * ph.n_leaves);
-      if (blk_verdict == 0) continue;
-    }
-    if (STAGE) {
-#if OBX_PIPELINE
-      stage_wait();
-      uint32_t b2 = b + gridDim.x;
-      if (b2 < n_blocks)
-        stage_issue(buf, blocks[b2],
-                    lds_blk + (par ^ 1) * OBX_LDS_STAGE_BYTES);
-#else
-      __syncthreads(); /* drain previous block's reads */
-      stage_issue(buf, cur, lds_blk);
-      stage_wait();
-#endif
-    }
+    const uint8_t blk_verdict = fold_prog3(ph, cur, plan_leaves, bl);
+    if (blk_verdict == 0) continue;
+    const blk_view bv = blk_open<STAGE>(buf, cur, lds_blk);
     const uint64_t blk_bit = cur.block_byte * 8;
-    blk_view bv;
-    bv.base = STAGE ? lds_blk + (OBX_PIPELINE ? par * OBX_LDS_STAGE_BYTES : 0)
-                    : buf;
-    bv.bit_bias = STAGE ? blk_bit : 0;
-    bv.rbase_bit = STAGE ? 0 : blk_bit;
-    par ^= 1;
 
     const uint32_t all_rows = cur.row_count;
-    const blk_leaf *bl = bleaves + (uint64_t)b * ph.n_leaves;
     for (uint32_t w0 = 0; w0 < all_rows; w0 += OBX_MAX_BLOCK_ROWS) {
     const uint32_t rows = (all_rows - w0 < OBX_MAX_BLOCK_ROWS)
                               ? all_rows - w0 : OBX_MAX_BLOCK_ROWS;
     const uint32_t iters = (rows + WG - 1) / WG;
 
-    /* ---- phase 1: filter into the LDS pass bitmap, one leaf at a time
-       (the reference's per-leaf bitmap combine, ob_pushdown_filter.cpp:1559;
-       a single live leaf context keeps uniform state inside the SGPR
-       budget). AND-only plans fold progressively; plans with a combine
-       program evaluate per-leaf bitmaps then a word-wise postfix pass. ---- */
-    if (blk_verdict == 1) {
-      for (uint32_t it = 0; it < iters; it++) {
-        uint32_t rr = it * WG + tid;
-        uint64_t m = __ballot(rr < rows);
-        if (lane == 0) pass_bm[it * WAVES + wv] = m;
-      }
-    } else if constexpr (!PROG) {
-      bool first = true;
-      for (uint32_t i = 0; i < ph.n_leaves; i++) {
-        const blk_leaf lfb = bl[i];
-        if (lfb.mode == OBX_LEAF_ALL &&
-            !(cur.cols[plan_leaves[i].col].flags & OBX_DF_HAS_EXT))
-          continue; /* every row passes this leaf */
-        leaf_ctx lc = make_leaf_ctx(cur, plan_leaves[i], bl[i], blk_bit);
-        const bool slow = lc.slow;
-        for (uint32_t it = 0; it < iters; it++) {
-          uint64_t prev = first ? ~0ull : pass_bm[it * WAVES + wv];
-          if (!prev) { if (first && lane == 0) pass_bm[it * WAVES + wv] = 0;
-                       continue; }
-          uint32_t rr = it * WG + tid;
-          uint32_t r = w0 + rr;
-          bool pass = rr < rows && ((prev >> lane) & 1);
-          if (pass)
-            pass = slow ? leaf_match(bv, cur, plan_leaves[i], bl[i], r)
-                        : leaf_ctx_match(bv, lc, plan_leaves[i], r);
-          uint64_t m = __ballot(pass);
-          if (lane == 0) pass_bm[it * WAVES + wv] = m;
-        }
-        first = false;
-      }
-      if (first) { /* no live leaves: all in-range rows pass */
-        for (uint32_t it = 0; it < iters; it++) {
-          uint32_t rr = it * WG + tid;
-          uint64_t m = __ballot(rr < rows);
-          if (lane == 0) pass_bm[it * WAVES + wv] = m;
-        }
-      }
-    } else {
-      prog_spec ps;
-      ps.n = ph.n_prog;
-      for (int p = 0; p < 15; p++) ps.t[p] = ph.prog[p];
-      filter_prog_phase(bv, cur, plan_leaves, bl, ph.n_leaves, ps, rows, w0,
-                        blk_bit, (lds3_u64 *)pass_bm,
-                        (lds3_u64 *)&u.leaf_bm[0][0]);
-    }
+    /* ---- phase 1: filter into the LDS pass bitmap ---- */
+    filter_window<PROG>(bv, cur, plan_leaves, bl, ph, blk_verdict, blk_bit,
+                        rows, w0, pass_bm, &u.leaf_bm[0][0]);
     /* rows-passed count (lane 0 of each wave over its own words) */
     for (uint32_t it = 0; it < iters; it++) {
       if (lane == 0) {
@@ -229,236 +473,68 @@ __device__ void scan_filter_agg_body(
     }
     __syncthreads();
 
-    /* ---- phase 2: group rows to LDS-table slots (row_slot map).
-       Fast path (the reference's storage group-by pushdown design,
-       ob_pushdown_aggregate_vec.h:445 / read_reference): when every group
-       column is dict-encoded and the ref product is small, rows map to
-       cells by packed REFS alone; cell -> slot resolves lazily, once per
-       block, via the dict values. NULL group values set flag bits in the
-       top key byte (data bytes stay zero). ---- */
     if (ph.n_aggs) {
-      col_ctx g0, g1;
-      const dev_col *gd0 = nullptr, *gd1 = nullptr;
-      if (ph.n_group_cols > 0) {
-        gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
-        g0 = make_col_ctx(*gd0, blk_bit);
-      }
-      if (ph.n_group_cols > 1) {
-        gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
-        g1 = make_col_ctx(*gd1, blk_bit);
-      }
-      const uint32_t kl0 = ph.group_len[0], kl1 = ph.group_len[1];
-      const uint32_t dim0 = (ph.n_group_cols > 0) ? g0.count + 1 : 1;
-      const uint32_t dim1 = (ph.n_group_cols > 1) ? g1.count + 1 : 1;
-      const bool ref_fast =
-          ph.n_group_cols > 0 && g0.kind == 1 &&
-          (ph.n_group_cols < 2 || g1.kind == 1) && dim0 * dim1 <= 64;
-
-      if (ref_fast) {
+      /* ---- phase 2: group rows to LDS-table slots (row_slot map) ---- */
+      const group_ctx g = group_open(ph, cur, blk_bit);
+      if (g.ref_fast) {
         for (uint32_t i = tid; i < 64; i += WG) cell_slot[i] = 254;
         __syncthreads();
-        for (uint32_t it = 0; it < iters; it++) {
-          uint32_t rr = it * WG + tid;
-          uint32_t r = w0 + rr;
-          uint64_t m = pass_bm[it * WAVES + wv];
-          bool pass = (m >> lane) & 1;
-          if (!m) { if (rr < rows) u.row_slot[rr] = 255; continue; }
-          uint8_t slot8 = 255;
-          if (pass) {
-            uint32_t ref0 = (uint32_t)bit_read_at(
-                bv.base, bv.rbase_bit + g0.data_bit + (uint64_t)r * g0.W,
-                g0.W);
-            if (ref0 > g0.count) ref0 = g0.count; /* nope -> null bucket */
-            uint32_t cell = ref0;
-            if (ph.n_group_cols > 1) {
-              uint32_t ref1 = (uint32_t)bit_read_at(
-                  bv.base, bv.rbase_bit + g1.data_bit + (uint64_t)r * g1.W,
-                  g1.W);
-              if (ref1 > g1.count) ref1 = g1.count;
-              cell += ref1 * dim0;
-            }
-            uint8_t cs = cell_slot[cell];
-            if (cs == 254) {
-              int s = lds_slot(&tab, build_group_key(bv, ph.n_group_cols,
-                                                      gd0, gd1, kl0, kl1,
-                                                      r));
-              if (s < 0) {
-                atomicAdd(&counters[1], 1ull);
-                cs = 255;
-              } else {
-                cs = (uint8_t)s;
-              }
-              cell_slot[cell] = cs;
-            }
-            slot8 = cs;
-            if (slot8 != 255)
-              atomicAdd(&tab.count[slot8][lane & (OBX_STRIPES - 1)], 1ull);
-          }
-          if (rr < rows) u.row_slot[rr] = slot8;
-        }
-      } else {
-        for (uint32_t it = 0; it < iters; it++) {
-          uint32_t rr = it * WG + tid;
-          uint32_t r = w0 + rr;
-          uint64_t m = pass_bm[it * WAVES + wv];
-          bool pass = (m >> lane) & 1;
-          if (!m) { if (rr < rows) u.row_slot[rr] = 255; continue; }
-          uint8_t slot8 = 255;
-          if (pass) {
-            int s = lds_slot(&tab, build_group_key(bv, ph.n_group_cols,
-                                                   gd0, gd1, kl0, kl1, r));
-            if (s < 0) {
-              atomicAdd(&counters[1], 1ull);
-            } else {
-              slot8 = (uint8_t)s;
-              atomicAdd(&tab.count[s][lane & (OBX_STRIPES - 1)], 1ull);
-            }
-          }
-          if (rr < rows) u.row_slot[rr] = slot8;
-        }
+      }
+      for (uint32_t it = 0; it < iters; it++) {
+        uint32_t rr = it * WG + tid;
+        uint64_t m = pass_bm[it * WAVES + wv];
+        if (!m) { if (rr < rows) u.row_slot[rr] = 255; continue; }
+        uint8_t slot8 = 255;
+        if ((m >> lane) & 1)
+          slot8 = group_row(
+              bv, ph, g, cell_slot, w0 + rr, counters,
+              [&](uint64_t key) { return lds_slot(&tab, key); },
+              [&](uint8_t s) { atomicAdd(&tab.count[s][stripe], 1ull); });
+        if (rr < rows) u.row_slot[rr] = slot8;
       }
       __syncthreads();
 
       /* ---- phase 3: one pass per aggregate (ctxs live one at a time).
-         The kind switch is hoisted OUT of the row loop; COUNT(*) needs no
+         The kind is a constant of each rows_of instantiation, so its
+         switch stays OUT of the row loop (measured); COUNT(*) needs no
          pass (filled from tab.count at flush); PROD2+PROD3 with shared
          inputs run as one fused pass. ---- */
       for (uint32_t a = 0; a < ph.n_aggs; a++) {
         const dev_agg ag = ph.aggs[a];
         if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*) at flush */
-        const bool fuse_p3 = (ag.kind == 4 && a + 1 < ph.n_aggs &&
-                              ph.aggs[a + 1].kind == 5 &&
-                              ph.aggs[a + 1].ia == ag.ia &&
-                              ph.aggs[a + 1].ib == ag.ib);
+        const bool fuse_p3 = obx_fuse_p3(ph.aggs, ph.n_aggs, a);
         const dev_agg ag2 = fuse_p3 ? ph.aggs[a + 1] : ag;
-        col_ctx ca, cb, cc;
-        const dev_col *da = nullptr, *db = nullptr, *dc2 = nullptr;
-        if (ag.ia != 0xFF) {
-          da = &cur.cols[ph.need_cols[ag.ia]];
-          ca = make_col_ctx(*da, blk_bit);
-        }
-        if (ag.ib != 0xFF) {
-          db = &cur.cols[ph.need_cols[ag.ib]];
-          cb = make_col_ctx(*db, blk_bit);
-        }
-        uint16_t ic = fuse_p3 ? ag2.ic : ag.ic;
-        if (ic != 0xFF && (ag.kind == 5 || fuse_p3)) {
-          dc2 = &cur.cols[ph.need_cols[ic]];
-          cc = make_col_ctx(*dc2, blk_bit);
-        }
-        const uint32_t stripe = lane & (OBX_STRIPES - 1);
-
-#define P3_LOOP(...)                                                   \
-        for (uint32_t it = 0; it < iters; it++) {                       \
-          uint32_t rr = it * WG + tid;                                  \
-          uint32_t r = w0 + rr;                                         \
-          uint64_t m = pass_bm[it * WAVES + wv];                        \
-          if (!m) continue;                                             \
-          bool pass = (m >> lane) & 1;                                  \
-          uint8_t slot8 = pass && rr < rows ? u.row_slot[rr] : 255;       \
-          if (slot8 == 255) continue;                                   \
-          int s = slot8;                                                \
-          (void)r; __VA_ARGS__                                          \
-        }
-
+        const agg_opnd oa = opnd_open(ph, cur, ag.ia, blk_bit);
+        const agg_opnd ob = opnd_open(ph, cur, ag.ib, blk_bit);
+        const agg_opnd oc = opnd_open(ph, cur, ag2.ic, blk_bit);
+        auto rows_of = [&](auto kind, auto fuse) {
+          for (uint32_t it = 0; it < iters; it++) {
+            uint32_t rr = it * WG + tid;
+            uint64_t m = pass_bm[it * WAVES + wv];
+            if (!m) continue;
+            bool pass = (m >> lane) & 1;
+            uint8_t slot8 = pass && rr < rows ? u.row_slot[rr] : 255;
+            if (slot8 == 255) continue;
+            agg_row(bv, cur, kind.v, fuse.v != 0, ag, ag2, oa, ob, oc,
+                    w0 + rr,
+                    lds_sink{tab.cell[slot8][a][stripe],
+                             fuse.v ? tab.cell[slot8][a + 1][stripe]
+                                    : nullptr});
+          }
+        };
         switch (ag.kind) {
-          case 0: { /* COUNT(col) */
-            P3_LOOP({
-              bool na;
-              (void)((ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                    : ctx_value(bv, ca, r, na));
-              if (!na)
-                atomicAdd(&tab.cell[s][a][stripe][0], 1ull);
-            })
+          case 0: rows_of(kc<0>{}, kc<0>{}); break; /* COUNT(col) */
+          case 1: rows_of(kc<1>{}, kc<0>{}); break; /* SUM */
+          case 2: rows_of(kc<2>{}, kc<0>{}); break; /* MIN */
+          case 3: rows_of(kc<3>{}, kc<0>{}); break; /* MAX */
+          case 4: /* SUM_PROD2, optionally with its PROD3 mate */
+            if (fuse_p3) rows_of(kc<4>{}, kc<1>{});
+            else rows_of(kc<4>{}, kc<0>{});
             break;
-          }
-          case 1: { /* SUM */
-            P3_LOOP({
-              bool na;
-              int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                          : ctx_value(bv, ca, r, na);
-              if (!na)
-                lds_acc_i128(tab.cell[s][a][stripe], i128_from_i64(va));
-            })
-            break;
-          }
-          case 2: case 3: { /* MIN / MAX */
-            const bool is_min = ag.kind == 2;
-            P3_LOOP({
-              bool na;
-              int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                          : ctx_value(bv, ca, r, na);
-              if (!na) {
-                cas_minmax(&tab.cell[s][a][stripe][0], va, is_min);
-                tab.cell[s][a][stripe][1] = 1;
-              }
-            })
-            break;
-          }
-          case 4: { /* SUM_PROD2 (optionally fused with a PROD3 mate) */
-            if (fuse_p3) {
-              P3_LOOP({
-                bool na, nb, nc;
-                int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                            : ctx_value(bv, ca, r, na);
-                int64_t vb = (cb.kind == 4) ? col_value2(bv, cur, *db, r, nb)
-                                            : ctx_value(bv, cb, r, nb);
-                int64_t vc = (cc.kind == 4) ? col_value2(bv, cur, *dc2, r, nc)
-                                            : ctx_value(bv, cc, r, nc);
-                if (!na && !nb) {
-                  i128v p2 = i128_mul_i64(va, ag.one_b - vb);
-                  lds_acc_i128(tab.cell[s][a][stripe], p2);
-                  if (!nc)
-                    lds_acc_i128(tab.cell[s][a + 1][stripe],
-                                 i128_mul_pos_i64(p2, ag2.one_c + vc));
-                }
-              })
-            } else {
-              P3_LOOP({
-                bool na, nb;
-                int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                            : ctx_value(bv, ca, r, na);
-                int64_t vb = (cb.kind == 4) ? col_value2(bv, cur, *db, r, nb)
-                                            : ctx_value(bv, cb, r, nb);
-                if (!na && !nb)
-                  lds_acc_i128(tab.cell[s][a][stripe],
-                               i128_mul_i64(va, ag.one_b - vb));
-              })
-            }
-            break;
-          }
-          case 5: { /* SUM_PROD3 standalone */
-            P3_LOOP({
-              bool na, nb, nc;
-              int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                          : ctx_value(bv, ca, r, na);
-              int64_t vb = (cb.kind == 4) ? col_value2(bv, cur, *db, r, nb)
-                                          : ctx_value(bv, cb, r, nb);
-              int64_t vc = (cc.kind == 4) ? col_value2(bv, cur, *dc2, r, nc)
-                                          : ctx_value(bv, cc, r, nc);
-              if (!na && !nb && !nc)
-                lds_acc_i128(tab.cell[s][a][stripe],
-                             i128_mul_pos_i64(i128_mul_i64(va,
-                                                           ag.one_b - vb),
-                                              ag.one_c + vc));
-            })
-            break;
-          }
-          case 6: { /* SUM_MUL */
-            P3_LOOP({
-              bool na, nb;
-              int64_t va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                                          : ctx_value(bv, ca, r, na);
-              int64_t vb = (cb.kind == 4) ? col_value2(bv, cur, *db, r, nb)
-                                          : ctx_value(bv, cb, r, nb);
-              if (!na && !nb)
-                lds_acc_i128(tab.cell[s][a][stripe], i128_mul_i64(va, vb));
-            })
-            break;
-          }
+          case 5: rows_of(kc<5>{}, kc<0>{}); break; /* SUM_PROD3 alone */
+          case 6: rows_of(kc<6>{}, kc<0>{}); break; /* SUM_MUL */
           default: break;
         }
-#undef P3_LOOP
         if (fuse_p3) a++; /* consumed the PROD3 mate */
       }
     }
@@ -472,41 +548,21 @@ __device__ void scan_filter_agg_body(
   for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
     uint64_t key = tab.key[s];
     if (key == OBX_KEY_EMPTY) continue;
-    uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - OBX_GTABLE_SHIFT)) &
-                   (OBX_GTABLE_SLOTS - 1);
-    for (int probe = 0; probe < OBX_GTABLE_SLOTS; probe++) {
-      unsigned long long cur_k = atomicCAS(&gtable[idx].key, OBX_KEY_EMPTY,
-                                           (unsigned long long)key);
-      if (cur_k == OBX_KEY_EMPTY || cur_k == key) break;
-      idx = (idx + 1) & (OBX_GTABLE_SLOTS - 1);
-    }
+    /* known gap: a full table (more than OBX_GTABLE_SLOTS distinct groups
+       with no workgroup overflowing its LDS table) has no result here; the
+       slot's count and cells then land in the key's home slot */
+    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
+    const uint32_t idx =
+        gi < 0 ? gtable_home<OBX_GTABLE_SHIFT>(key) : (uint32_t)gi;
     unsigned long long cnt = 0;
     for (uint32_t st = 0; st < OBX_STRIPES; st++) cnt += tab.count[s][st];
     atomicAdd(&gtable[idx].count, cnt);
     for (uint32_t a = 0; a < ph.n_aggs; a++) {
       uint8_t kind = ph.aggs[a].kind;
-      if (kind == 0 && ph.aggs[a].ia == 0xFF) {
-        /* COUNT(*): equals the group's row count */
+      if (kind == 0 && ph.aggs[a].ia == 0xFF) /* COUNT(*): the row count */
         g_acc_i128(gtable[idx].cells[a], cnt, 0);
-      } else if (kind == 2 || kind == 3) {
-        for (uint32_t st = 0; st < OBX_STRIPES; st++) {
-          if (tab.cell[s][a][st][1]) {
-            cas_minmax(&gtable[idx].cells[a][0],
-                       (int64_t)tab.cell[s][a][st][0], kind == 2);
-            gtable[idx].cells[a][1] = 1;
-          }
-        }
-      } else {
-        /* sum the 4 striped int128 partials, then one 256-bit accumulate */
-        uint64_t lo = 0, hi = 0;
-        for (uint32_t st = 0; st < OBX_STRIPES; st++) {
-          uint64_t l = tab.cell[s][a][st][0];
-          uint64_t nlo = lo + l;
-          hi += tab.cell[s][a][st][1] + (nlo < l);
-          lo = nlo;
-        }
-        g_acc_i128(gtable[idx].cells[a], lo, hi);
-      }
+      else
+        flush_cells<OBX_STRIPES>(tab.cell[s][a], kind, gtable[idx].cells[a]);
     }
   }
 }
@@ -534,7 +590,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_filter_agg_lds(
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
     gslot *__restrict__ gtable, unsigned long long *__restrict__ counters) {
-  __shared__ uint8_t lds_blk[(1 + OBX_PIPELINE) * OBX_LDS_STAGE_BYTES + 32];
+  __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
   scan_filter_agg_body<true, false>(buf, blocks, n_blocks, plan_leaves,
                                     bleaves, ph, gtable, counters, lds_blk);
 }
@@ -544,7 +600,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_filter_agg_prog_lds(
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
     gslot *__restrict__ gtable, unsigned long long *__restrict__ counters) {
-  __shared__ uint8_t lds_blk[(1 + OBX_PIPELINE) * OBX_LDS_STAGE_BYTES + 32];
+  __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
   scan_filter_agg_body<true, true>(buf, blocks, n_blocks, plan_leaves,
                                    bleaves, ph, gtable, counters, lds_blk);
 }
@@ -571,100 +627,29 @@ __device__ void filter_body(
   if (tid == 0) wg_passed = 0;
   __syncthreads();
 
-  uint32_t par = 0;
-  if (STAGE && OBX_PIPELINE && blockIdx.x < n_blocks)
-    stage_issue(buf, blocks[blockIdx.x], lds_blk);
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
     const dev_block &cur = blocks[b];
-    uint8_t blk_verdict = 2;
-    if (!OBX_PIPELINE || !STAGE) {
-      /* constant-result short-circuit (see scan_filter_agg_body) */
-      blk_verdict = fold_prog3(ph, cur, plan_leaves,
-                               bleaves + (uint64_t)b * ph.n_leaves);
-      if (blk_verdict == 0) {
-        if (row_ids && tid == 0) blk_counts[b] = 0;
-        continue; /* bitmap is pre-zeroed */
-      }
+    const blk_leaf *bl = bleaves + (uint64_t)b * ph.n_leaves;
+    /* constant-result short-circuit (see scan_filter_agg_body) */
+    const uint8_t blk_verdict = fold_prog3(ph, cur, plan_leaves, bl);
+    if (blk_verdict == 0) {
+      if (row_ids && tid == 0) blk_counts[b] = 0;
+      continue; /* bitmap is pre-zeroed */
     }
     if (tid == 0) blk_written = 0;
-    if (STAGE) {
-#if OBX_PIPELINE
-      stage_wait();
-      uint32_t b2 = b + gridDim.x;
-      if (b2 < n_blocks)
-        stage_issue(buf, blocks[b2],
-                    lds_blk + (par ^ 1) * OBX_LDS_STAGE_BYTES);
-#else
-      __syncthreads();
-      stage_issue(buf, cur, lds_blk);
-      stage_wait();
-#endif
-    } else {
-      __syncthreads(); /* blk_written reset */
-    }
+    const blk_view bv = blk_open<STAGE>(buf, cur, lds_blk);
+    if (!STAGE) __syncthreads(); /* blk_written reset */
     const uint64_t blk_bit = cur.block_byte * 8;
-    blk_view bv;
-    bv.base = STAGE ? lds_blk + (OBX_PIPELINE ? par * OBX_LDS_STAGE_BYTES : 0)
-                    : buf;
-    bv.bit_bias = STAGE ? blk_bit : 0;
-    bv.rbase_bit = STAGE ? 0 : blk_bit;
-    par ^= 1;
 
     const uint32_t all_rows = cur.row_count;
     const uint64_t row_start = dev_block_row_start(&cur);
-    const blk_leaf *bl = bleaves + (uint64_t)b * ph.n_leaves;
     for (uint32_t w0 = 0; w0 < all_rows; w0 += OBX_MAX_BLOCK_ROWS) {
     const uint32_t rows = (all_rows - w0 < OBX_MAX_BLOCK_ROWS)
                               ? all_rows - w0 : OBX_MAX_BLOCK_ROWS;
     const uint32_t iters = (rows + WG - 1) / WG;
 
-    /* leaf-by-leaf fission into the pass bitmap (one live context);
-       combine programs evaluate per-leaf bitmaps then a word-wise postfix */
-    if (blk_verdict == 1) {
-      for (uint32_t it = 0; it < iters; it++) {
-        uint32_t rr = it * WG + tid;
-        uint64_t m = __ballot(rr < rows);
-        if (lane == 0) pass_bm[it * WAVES + wv] = m;
-      }
-    } else if constexpr (!PROG) {
-      bool first = true;
-      for (uint32_t i = 0; i < ph.n_leaves; i++) {
-        const blk_leaf lfb = bl[i];
-        if (lfb.mode == OBX_LEAF_ALL &&
-            !(cur.cols[plan_leaves[i].col].flags & OBX_DF_HAS_EXT))
-          continue;
-        leaf_ctx lc = make_leaf_ctx(cur, plan_leaves[i], bl[i], blk_bit);
-        const bool slow = lc.slow;
-        for (uint32_t it = 0; it < iters; it++) {
-          uint64_t prev = first ? ~0ull : pass_bm[it * WAVES + wv];
-          if (!prev) { if (first && lane == 0) pass_bm[it * WAVES + wv] = 0;
-                       continue; }
-          uint32_t rr = it * WG + tid;
-          uint32_t r = w0 + rr;
-          bool pass = rr < rows && ((prev >> lane) & 1);
-          if (pass)
-            pass = slow ? leaf_match(bv, cur, plan_leaves[i], bl[i], r)
-                        : leaf_ctx_match(bv, lc, plan_leaves[i], r);
-          uint64_t m = __ballot(pass);
-          if (lane == 0) pass_bm[it * WAVES + wv] = m;
-        }
-        first = false;
-      }
-      if (first) {
-        for (uint32_t it = 0; it < iters; it++) {
-          uint32_t rr = it * WG + tid;
-          uint64_t m = __ballot(rr < rows);
-          if (lane == 0) pass_bm[it * WAVES + wv] = m;
-        }
-      }
-    } else {
-      prog_spec ps;
-      ps.n = ph.n_prog;
-      for (int p = 0; p < 15; p++) ps.t[p] = ph.prog[p];
-      filter_prog_phase(bv, cur, plan_leaves, bl, ph.n_leaves, ps, rows, w0,
-                        blk_bit, (lds3_u64 *)pass_bm,
-                        (lds3_u64 *)&leaf_bm[0][0]);
-    }
+    filter_window<PROG>(bv, cur, plan_leaves, bl, ph, blk_verdict, blk_bit,
+                        rows, w0, pass_bm, &leaf_bm[0][0]);
 
     /* output: global bitmap words, pass counts, selection vectors */
     for (uint32_t it = 0; it < iters; it++) {
@@ -747,7 +732,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_filter_lds(
     uint64_t *__restrict__ bitmap, int32_t *__restrict__ row_ids,
     uint32_t *__restrict__ blk_counts,
     unsigned long long *__restrict__ counters) {
-  __shared__ uint8_t lds_blk[(1 + OBX_PIPELINE) * OBX_LDS_STAGE_BYTES + 32];
+  __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
   filter_body<true, false>(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
                            bitmap, row_ids, blk_counts, counters, lds_blk);
 }
@@ -759,37 +744,48 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_filter_prog_lds(
     uint64_t *__restrict__ bitmap, int32_t *__restrict__ row_ids,
     uint32_t *__restrict__ blk_counts,
     unsigned long long *__restrict__ counters) {
-  __shared__ uint8_t lds_blk[(1 + OBX_PIPELINE) * OBX_LDS_STAGE_BYTES + 32];
+  __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
   filter_body<true, true>(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
                           bitmap, row_ids, blk_counts, counters, lds_blk);
 }
 
-/* ---------------- decode kernel (get_rows equivalent, parity) ----------- */
+/* ---------------- decode kernels (get_rows equivalent, parity) ---------- */
+/* every row of one column of an open block -> datums and null bytes */
+__device__ __forceinline__ void decode_rows(const blk_view &bv,
+                                            const dev_block &cur,
+                                            uint32_t col, uint32_t datum_len,
+                                            uint8_t *__restrict__ out,
+                                            uint8_t *__restrict__ out_null) {
+  const uint32_t rows = cur.row_count;
+  const uint64_t row_start = dev_block_row_start(&cur);
+  for (uint32_t r = threadIdx.x; r < rows; r += WG) {
+    bool isn;
+    int64_t v = col_value2(bv, cur, cur.cols[col], r, isn);
+    store_datum(out + (row_start + r) * datum_len, isn ? 0 : (uint64_t)v,
+                datum_len);
+    if (out_null) out_null[row_start + r] = isn ? 1 : 0;
+  }
+}
+
+template <bool STAGE>
+__device__ __forceinline__ void decode_body(
+    const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
+    uint32_t n_blocks, uint32_t col, uint32_t datum_len,
+    uint8_t *__restrict__ out, uint8_t *__restrict__ out_null,
+    uint8_t *lds_blk) {
+  for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    const dev_block &cur = blocks[b];
+    const blk_view bv = blk_open<STAGE>(buf, cur, lds_blk);
+    decode_rows(bv, cur, col, datum_len, out, out_null);
+  }
+}
+
 extern "C" __global__ __launch_bounds__(WG, 2) void k_decode(
     const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
     uint32_t n_blocks, uint32_t col, uint32_t datum_len,
     uint8_t *__restrict__ out, uint8_t *__restrict__ out_null) {
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    const dev_block &cur = blocks[b];
-    blk_view bv; bv.base = buf; bv.bit_bias = 0; bv.rbase_bit = 0;
-    const uint32_t rows = cur.row_count;
-    const uint64_t row_start = dev_block_row_start(&cur);
-    for (uint32_t r = tid; r < rows; r += WG) {
-      bool isn;
-      int64_t v = col_value2(bv, cur, cur.cols[col], r, isn);
-      uint64_t uv = isn ? 0 : (uint64_t)v;
-      uint8_t *dst = out + (row_start + r) * datum_len;
-      if (datum_len == 8)       /* aligned: hipMalloc base + 8-B stride */
-        *(uint64_t *)dst = uv;
-      else if (datum_len == 4)
-        *(uint32_t *)dst = (uint32_t)uv;
-      else
-        for (uint32_t i = 0; i < datum_len; i++)
-          dst[i] = (uint8_t)(uv >> (i * 8));
-      if (out_null) out_null[row_start + r] = isn ? 1 : 0;
-    }
-  }
+  decode_body<false>(buf, blocks, n_blocks, col, datum_len, out, out_null,
+                     nullptr);
 }
 
 extern "C" __global__ __launch_bounds__(WG, 2) void k_decode_lds(
@@ -800,33 +796,8 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_decode_lds(
      (the global-read variant measured ~0.8 TB/s; staging reads the
      encoded bytes once, coalesced) */
   __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    const dev_block &cur = blocks[b];
-    __syncthreads(); /* drain previous block's LDS reads */
-    stage_issue(buf, cur, lds_blk);
-    stage_wait();
-    blk_view bv;
-    bv.base = lds_blk;
-    bv.bit_bias = cur.block_byte * 8;
-    bv.rbase_bit = 0;
-    const uint32_t rows = cur.row_count;
-    const uint64_t row_start = dev_block_row_start(&cur);
-    for (uint32_t r = tid; r < rows; r += WG) {
-      bool isn;
-      int64_t v = col_value2(bv, cur, cur.cols[col], r, isn);
-      uint64_t uv = isn ? 0 : (uint64_t)v;
-      uint8_t *dst = out + (row_start + r) * datum_len;
-      if (datum_len == 8)       /* aligned: hipMalloc base + 8-B stride */
-        *(uint64_t *)dst = uv;
-      else if (datum_len == 4)
-        *(uint32_t *)dst = (uint32_t)uv;
-      else
-        for (uint32_t i = 0; i < datum_len; i++)
-          dst[i] = (uint8_t)(uv >> (i * 8));
-      if (out_null) out_null[row_start + r] = isn ? 1 : 0;
-    }
-  }
+  decode_body<true>(buf, blocks, n_blocks, col, datum_len, out, out_null,
+                    lds_blk);
 }
 
 extern "C" __global__ __launch_bounds__(WG, 2) void k_decode_multi(
@@ -837,38 +808,12 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_decode_multi(
   /* one stage per block, ALL projected columns decoded from LDS — the
      per-column variant re-reads every block once per column */
   __shared__ uint8_t lds_blk[OBX_LDS_STAGE_BYTES + 32];
-  const uint32_t tid = threadIdx.x;
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
     const dev_block &cur = blocks[b];
-    __syncthreads(); /* drain previous block's LDS reads */
-    stage_issue(buf, cur, lds_blk);
-    stage_wait();
-    blk_view bv;
-    bv.base = lds_blk;
-    bv.bit_bias = cur.block_byte * 8;
-    bv.rbase_bit = 0;
-    const uint32_t rows = cur.row_count;
-    const uint64_t row_start = dev_block_row_start(&cur);
-    for (uint32_t p = 0; p < n_proj; p++) {
-      const uint32_t col = proj[p];
-      const uint32_t datum_len = lens[p];
-      uint8_t *out = outs[p];
-      uint8_t *out_null = onulls ? onulls[p] : nullptr;
-      for (uint32_t r = tid; r < rows; r += WG) {
-        bool isn;
-        int64_t v = col_value2(bv, cur, cur.cols[col], r, isn);
-        uint64_t uv = isn ? 0 : (uint64_t)v;
-        uint8_t *dst = out + (row_start + r) * datum_len;
-        if (datum_len == 8)
-          *(uint64_t *)dst = uv;
-        else if (datum_len == 4)
-          *(uint32_t *)dst = (uint32_t)uv;
-        else
-          for (uint32_t i = 0; i < datum_len; i++)
-            dst[i] = (uint8_t)(uv >> (i * 8));
-        if (out_null) out_null[row_start + r] = isn ? 1 : 0;
-      }
-    }
+    const blk_view bv = blk_open<true>(buf, cur, lds_blk);
+    for (uint32_t p = 0; p < n_proj; p++)
+      decode_rows(bv, cur, proj[p], lens[p], outs[p],
+                  onulls ? onulls[p] : nullptr);
   }
 }
 
@@ -1282,24 +1227,6 @@ extern "C" __global__ void k_col_minmax(
  * them as u8 (255 = filtered out or table overflow; overflow counted).
  * ====================================================================== */
 
-/* find-or-insert a key in the global group table; returns slot or -1 */
-__device__ __forceinline__ int g_slot(gslot *gtable, uint64_t key) {
-  uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - OBX_GTABLE_SHIFT)) &
-                 (OBX_GTABLE_SLOTS - 1);
-  for (int probe = 0; probe < OBX_GTABLE_SLOTS; probe++) {
-    unsigned long long k = __hip_atomic_load(
-        &gtable[idx].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == key) return (int)idx;
-    if (k == OBX_KEY_EMPTY) {
-      unsigned long long cur = atomicCAS(&gtable[idx].key, OBX_KEY_EMPTY,
-                                         (unsigned long long)key);
-      if (cur == OBX_KEY_EMPTY || cur == key) return (int)idx;
-    }
-    idx = (idx + 1) & (OBX_GTABLE_SLOTS - 1);
-  }
-  return -1;
-}
-
 /* this row's bit from the global survivor bitmap */
 __device__ __forceinline__ bool pass_bit(const uint64_t *__restrict__ bitmap,
                                          uint64_t grow) {
@@ -1324,29 +1251,11 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_group_pass(
 
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
     const dev_block &cur = blocks[b];
-    const uint64_t blk_bit = cur.block_byte * 8;
-    blk_view bv;
-    bv.base = buf; bv.bit_bias = 0; bv.rbase_bit = blk_bit;
+    const blk_view bv = blk_open<false>(buf, cur, nullptr);
     const uint32_t rows = cur.row_count;
     const uint64_t row_start = dev_block_row_start(&cur);
-
-    col_ctx g0, g1;
-    const dev_col *gd0 = nullptr, *gd1 = nullptr;
-    if (ph.n_group_cols > 0) {
-      gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
-      g0 = make_col_ctx(*gd0, blk_bit);
-    }
-    if (ph.n_group_cols > 1) {
-      gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
-      g1 = make_col_ctx(*gd1, blk_bit);
-    }
-    const uint32_t kl0 = ph.group_len[0], kl1 = ph.group_len[1];
-    const uint32_t dim0 = (ph.n_group_cols > 0) ? g0.count + 1 : 1;
-    const uint32_t dim1 = (ph.n_group_cols > 1) ? g1.count + 1 : 1;
-    const bool ref_fast = ph.n_group_cols > 0 && g0.kind == 1 &&
-                          (ph.n_group_cols < 2 || g1.kind == 1) &&
-                          dim0 * dim1 <= 64;
-    if (ref_fast) {
+    const group_ctx g = group_open(ph, cur, cur.block_byte * 8);
+    if (g.ref_fast) {
       __syncthreads(); /* previous block's cell reads drain */
       for (uint32_t i = tid; i < 64; i += WG) cell_slot[i] = 254;
       __syncthreads();
@@ -1356,42 +1265,14 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_group_pass(
     for (uint32_t it = 0; it < iters; it++) {
       uint32_t r = it * WG + tid;
       bool in = r < rows;
-      bool pass = in && pass_bit(bitmap, row_start + r);
       uint8_t slot8 = 255;
-      if (pass) {
-        if (ref_fast) {
-          uint32_t ref0 = (uint32_t)bit_read_at(
-              bv.base, bv.rbase_bit + g0.data_bit + (uint64_t)r * g0.W,
-              g0.W);
-          if (ref0 > g0.count) ref0 = g0.count;
-          uint32_t cell = ref0;
-          if (ph.n_group_cols > 1) {
-            uint32_t ref1 = (uint32_t)bit_read_at(
-                bv.base, bv.rbase_bit + g1.data_bit + (uint64_t)r * g1.W,
-                g1.W);
-            if (ref1 > g1.count) ref1 = g1.count;
-            cell += ref1 * dim0;
-          }
-          uint8_t cs = cell_slot[cell];
-          if (cs == 254) {
-            int s = g_slot(gtable, build_group_key(bv, ph.n_group_cols,
-                                                   gd0, gd1, kl0, kl1, r));
-            cs = (s < 0 || s >= 255) ? 255 : (uint8_t)s;
-            if (cs == 255) atomicAdd(&counters[1], 1ull);
-            cell_slot[cell] = cs;
-          }
-          slot8 = cs;
-        } else {
-          int s = g_slot(gtable, build_group_key(bv, ph.n_group_cols, gd0,
-                                                 gd1, kl0, kl1, r));
-          if (s < 0 || s >= 255) {
-            atomicAdd(&counters[1], 1ull);
-          } else {
-            slot8 = (uint8_t)s;
-          }
-        }
-        if (slot8 != 255) atomicAdd(&cnt[slot8][lane & 3], 1ull);
-      }
+      if (in && pass_bit(bitmap, row_start + r))
+        slot8 = group_row(
+            bv, ph, g, cell_slot, r, counters,
+            [&](uint64_t key) {
+              return gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
+            },
+            [&](uint8_t s) { atomicAdd(&cnt[s][lane & 3], 1ull); });
       if (in) row_slot[row_start + r] = slot8;
     }
   }
@@ -1411,15 +1292,11 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_agg_pass(
   /* per-slot LDS cells for this pass's aggregate(s): [slot][stripe][2] */
   __shared__ unsigned long long cells[2][OBX_GTABLE_SLOTS][4][2];
   const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63;
-  const uint32_t stripe = lane & 3;
+  const uint32_t stripe = tid & 3;
 
   const dev_agg ag = ph.aggs[a];
-  const bool fuse_p3 =
-      (ag.kind == 4 && a + 1 < ph.n_aggs && ph.aggs[a + 1].kind == 5 &&
-       ph.aggs[a + 1].ia == ag.ia && ph.aggs[a + 1].ib == ag.ib);
+  const bool fuse_p3 = obx_fuse_p3(ph.aggs, ph.n_aggs, a);
   const dev_agg ag2 = fuse_p3 ? ph.aggs[a + 1] : ag;
-  const bool is_minmax = (ag.kind == 2 || ag.kind == 3);
 
   for (uint32_t s = tid; s < OBX_GTABLE_SLOTS; s += WG) {
     for (uint32_t f = 0; f < 2; f++) {
@@ -1433,111 +1310,30 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_agg_pass(
   }
   __syncthreads();
 
-  unsigned long long *c0 = &cells[0][0][0][0];
-  unsigned long long *c1 = &cells[1][0][0][0];
-
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
     const dev_block &cur = blocks[b];
+    const blk_view bv = blk_open<false>(buf, cur, nullptr);
     const uint64_t blk_bit = cur.block_byte * 8;
-    blk_view bv;
-    bv.base = buf; bv.bit_bias = 0; bv.rbase_bit = blk_bit;
     const uint32_t rows = cur.row_count;
     const uint64_t row_start = dev_block_row_start(&cur);
+    const agg_opnd oa = opnd_open(ph, cur, ag.ia, blk_bit);
+    const agg_opnd ob = opnd_open(ph, cur, ag.ib, blk_bit);
+    const agg_opnd oc = opnd_open(ph, cur, ag2.ic, blk_bit);
 
-    col_ctx ca, cb, cc;
-    const dev_col *da = nullptr, *db = nullptr, *dc2 = nullptr;
-    if (ag.ia != 0xFF) {
-      da = &cur.cols[ph.need_cols[ag.ia]];
-      ca = make_col_ctx(*da, blk_bit);
-    }
-    if (ag.ib != 0xFF) {
-      db = &cur.cols[ph.need_cols[ag.ib]];
-      cb = make_col_ctx(*db, blk_bit);
-    }
-    uint16_t icx = fuse_p3 ? ag2.ic : ag.ic;
-    if (icx != 0xFF && (ag.kind == 5 || fuse_p3)) {
-      dc2 = &cur.cols[ph.need_cols[icx]];
-      cc = make_col_ctx(*dc2, blk_bit);
-    }
-
-    const uint32_t iters = (rows + WG - 1) / WG;
-    for (uint32_t it = 0; it < iters; it++) {
-      uint32_t r = it * WG + tid;
-      if (r >= rows) continue;
+    for (uint32_t r = tid; r < rows; r += WG) {
       uint8_t slot8 = row_slot[row_start + r];
       if (slot8 == 255) continue;
-      uint32_t idx = ((uint32_t)slot8 * 4 + stripe) * 2;
-      bool na = false, nb = false, nc = false;
-      int64_t va = 0, vb = 0, vc = 0;
-      if (ag.ia != 0xFF)
-        va = (ca.kind == 4) ? col_value2(bv, cur, *da, r, na)
-                            : ctx_value(bv, ca, r, na);
-      if (ag.ib != 0xFF)
-        vb = (cb.kind == 4) ? col_value2(bv, cur, *db, r, nb)
-                            : ctx_value(bv, cb, r, nb);
-      if (dc2)
-        vc = (cc.kind == 4) ? col_value2(bv, cur, *dc2, r, nc)
-                            : ctx_value(bv, cc, r, nc);
-      switch (ag.kind) {
-        case 0: /* COUNT(col) */
-          if (!na) atomicAdd(&c0[idx], 1ull);
-          break;
-        case 1: /* SUM */
-          if (!na) lds_acc_i128(&c0[idx], i128_from_i64(va));
-          break;
-        case 2: case 3: /* MIN/MAX */
-          if (!na) {
-            cas_minmax(&c0[idx], va, ag.kind == 2);
-            c0[idx + 1] = 1;
-          }
-          break;
-        case 4: /* SUM_PROD2 (+ fused PROD3 mate) */
-          if (!na && !nb) {
-            i128v p2 = i128_mul_i64(va, ag.one_b - vb);
-            lds_acc_i128(&c0[idx], p2);
-            if (fuse_p3 && !nc)
-              lds_acc_i128(&c1[idx], i128_mul_pos_i64(p2, ag2.one_c + vc));
-          }
-          break;
-        case 5: /* SUM_PROD3 standalone */
-          if (!na && !nb && !nc)
-            lds_acc_i128(&c0[idx],
-                         i128_mul_pos_i64(i128_mul_i64(va, ag.one_b - vb),
-                                          ag.one_c + vc));
-          break;
-        case 6: /* SUM_MUL */
-          if (!na && !nb) lds_acc_i128(&c0[idx], i128_mul_i64(va, vb));
-          break;
-        default: break;
-      }
+      agg_row(bv, cur, ag.kind, fuse_p3, ag, ag2, oa, ob, oc, r,
+              lds_sink{cells[0][slot8][stripe], cells[1][slot8][stripe]});
     }
   }
   __syncthreads();
 
-  /* flush: merge the two lane stripes, one global accumulate per slot */
-  for (uint32_t s = tid; s < OBX_GTABLE_SLOTS; s += WG) {
-    for (uint32_t f = 0; f < (fuse_p3 ? 2u : 1u); f++) {
-      uint32_t aa = a + f;
-      if (is_minmax) {
-        for (uint32_t st = 0; st < 4; st++) {
-          if (cells[f][s][st][1]) {
-            cas_minmax(&gtable[s].cells[aa][0],
-                       (int64_t)cells[f][s][st][0], ag.kind == 2);
-            gtable[s].cells[aa][1] = 1;
-          }
-        }
-      } else {
-        uint64_t lo = 0, hi = 0;
-        for (uint32_t st = 0; st < 4; st++) {
-          uint64_t l = cells[f][s][st][0];
-          uint64_t nlo = lo + l;
-          hi += cells[f][s][st][1] + (nlo < l);
-          lo = nlo;
-        }
-        if (lo | hi) g_acc_i128(gtable[s].cells[aa], lo, hi);
-      }
-    }
-  }
+  /* flush: merge the lane stripes, one global accumulate per slot */
+  for (uint32_t s = tid; s < OBX_GTABLE_SLOTS; s += WG)
+    for (uint32_t f = 0; f < (fuse_p3 ? 2u : 1u); f++)
+      flush_cells<4>(cells[f][s], ph.aggs[a + f].kind,
+                     gtable[s].cells[a + f]);
 }
 
 /* ---------------- high-cardinality direct-global scan --------------------
@@ -1546,27 +1342,10 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_agg_pass(
  * ob_exec_hash_struct_vec.h:1718): when the generic kernel reports an LDS
  * table overflow, the host reruns the scan with this kernel. No LDS
  * table: every surviving row probes the global group table (open
- * addressing over OBX_GTABLE_SLOTS) and accumulates with global atomics.
- * Correctness-first slow path — plans that fit the LDS table never take
- * it. AND-combined leaves only (the host keeps OBX_BUF_NOT_ENOUGH for
- * OR-programs). */
-__device__ __forceinline__ int g_slot_probe(gslot *gt, uint64_t key) {
-  uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >>
-                            (64 - OBX_GTABLE_BIG_SHIFT)) &
-                 (OBX_GTABLE_BIG - 1);
-  for (int p = 0; p < OBX_GTABLE_BIG; p++) {
-    unsigned long long k = gt[idx].key;
-    if (k == key) return (int)idx;
-    if (k == OBX_KEY_EMPTY) {
-      unsigned long long c = atomicCAS(&gt[idx].key, OBX_KEY_EMPTY,
-                                       (unsigned long long)key);
-      if (c == OBX_KEY_EMPTY || c == key) return (int)idx;
-    }
-    idx = (idx + 1) & (OBX_GTABLE_BIG - 1);
-  }
-  return -1;
-}
-
+ * addressing over OBX_GTABLE_BIG) and accumulates with global atomics,
+ * each aggregate on its own (no PROD2+PROD3 fusing). Correctness-first
+ * slow path — plans that fit the LDS table never take it. AND-combined
+ * leaves only (the host keeps OBX_BUF_NOT_ENOUGH for OR-programs). */
 extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
     const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
@@ -1582,10 +1361,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
     for (uint32_t i = 0; i < ph.n_leaves; i++)
       if (leaf_class(cur, plan_leaves[i], bl[i]) == 0) { skip = true; break; }
     if (skip) continue;
-    blk_view bv;
-    bv.base = buf;
-    bv.bit_bias = 0;
-    bv.rbase_bit = 0;
+    const blk_view bv = blk_open<false>(buf, cur, nullptr);
     const dev_col *gd0 = nullptr, *gd1 = nullptr;
     if (ph.n_group_cols > 0) gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
     if (ph.n_group_cols > 1) gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
@@ -1599,7 +1375,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
       lane_cnt++;
       uint64_t key = build_group_key(bv, ph.n_group_cols, gd0, gd1, kl0,
                                      kl1, r);
-      int gi = g_slot_probe(gtable, key);
+      int gi = gtable_slot<OBX_GTABLE_BIG_SHIFT>(gtable, key);
       if (gi < 0) { /* global table full: surfaced as counters[2] */
         atomicAdd(&counters[2], 1ull);
         continue;
@@ -1616,45 +1392,8 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
           vb = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ib]], r, nb);
         if (ag.kind == 5 && ag.ic != 0xFF)
           vc = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ic]], r, nc);
-        switch (ag.kind) {
-          case 0: /* COUNT(col) */
-            if (!na) g_acc_i128(gtable[gi].cells[a], 1ull, 0ull);
-            break;
-          case 1: /* SUM */
-            if (!na) {
-              i128v v = i128_from_i64(va);
-              g_acc_i128(gtable[gi].cells[a], v.lo, (uint64_t)v.hi);
-            }
-            break;
-          case 2:
-          case 3: /* MIN / MAX */
-            if (!na) {
-              cas_minmax(&gtable[gi].cells[a][0], va, ag.kind == 2);
-              gtable[gi].cells[a][1] = 1;
-            }
-            break;
-          case 4: /* SUM_PROD2 */
-            if (!na && !nb) {
-              i128v p2 = i128_mul_i64(va, ag.one_b - vb);
-              g_acc_i128(gtable[gi].cells[a], p2.lo, (uint64_t)p2.hi);
-            }
-            break;
-          case 5: /* SUM_PROD3 */
-            if (!na && !nb && !nc) {
-              i128v p3 = i128_mul_pos_i64(i128_mul_i64(va, ag.one_b - vb),
-                                          ag.one_c + vc);
-              g_acc_i128(gtable[gi].cells[a], p3.lo, (uint64_t)p3.hi);
-            }
-            break;
-          case 6: /* SUM_MUL */
-            if (!na && !nb) {
-              i128v p = i128_mul_i64(va, vb);
-              g_acc_i128(gtable[gi].cells[a], p.lo, (uint64_t)p.hi);
-            }
-            break;
-          default:
-            break;
-        }
+        agg_term(ag.kind, false, ag.one_b, ag.one_c, va, na, vb, nb, vc, nc,
+                 gcell_sink{gtable[gi].cells[a]});
       }
     }
   }

@@ -11,7 +11,7 @@
  * A translation unit of its own, so the scan kernels of obx_kernels.hip keep
  * their code and register allocation.
  */
-#include "obx_dev_common.h"
+#include "obx_blk.h"
 #include "obx_project.h"
 
 __device__ __forceinline__ uint64_t shflup64(uint64_t v, uint32_t d) {
@@ -113,18 +113,7 @@ __device__ __forceinline__ void project_sel_body(
     uint32_t cnt = row_ids ? blk_counts[b] : rows;
     if (cnt > rows) cnt = rows;
     if (cnt == 0) continue;
-    blk_view bv;
-    if (STAGE) {
-      __syncthreads(); /* drain previous block's LDS reads */
-      stage_issue(buf, cur, lds_blk);
-      stage_wait();
-      bv.base = lds_blk;
-      bv.bit_bias = cur.block_byte * 8;
-    } else {
-      bv.base = buf;
-      bv.bit_bias = 0;
-    }
-    bv.rbase_bit = 0;
+    const blk_view bv = blk_open<STAGE>(buf, cur, lds_blk);
     const uint64_t row_start = dev_block_row_start(&cur);
     const uint64_t o = row_ids ? off[b] : row_start;
     /* (loading several row ids per lane ahead of the decode calls was
@@ -139,15 +128,8 @@ __device__ __forceinline__ void project_sel_body(
         const uint32_t datum_len = pa.len[p];
         bool isn;
         int64_t v = col_value2(bv, cur, cur.cols[pa.col[p]], r, isn);
-        uint64_t uv = isn ? 0 : (uint64_t)v;
-        uint8_t *dst = pa.out[p] + dst_row * datum_len;
-        if (datum_len == 8)       /* aligned: hipMalloc base + 8-B stride */
-          *(uint64_t *)dst = uv;
-        else if (datum_len == 4)
-          *(uint32_t *)dst = (uint32_t)uv;
-        else
-          for (uint32_t k = 0; k < datum_len; k++)
-            dst[k] = (uint8_t)(uv >> (k * 8));
+        store_datum(pa.out[p] + dst_row * datum_len, isn ? 0 : (uint64_t)v,
+                    datum_len);
         nullmask |= (isn ? 1u : 0u) << p;
       }
       out_nulls[dst_row] = (uint8_t)nullmask;

@@ -28,6 +28,7 @@
 #include "obx_format.h"
 #include "../include/obx.h"
 
+#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -45,14 +46,19 @@
  * before trusting interior payloads (check_payload_checksum,
  * ob_micro_block_header.cpp:257-271). */
 static uint32_t crc32c_tab[256];
-static void crc32c_init(void) {
-  if (crc32c_tab[1]) return;
+static pthread_once_t crc32c_once = PTHREAD_ONCE_INIT;
+static void crc32c_fill(void) {
   for (uint32_t n = 0; n < 256; n++) {
     uint32_t c = n;
     for (int k = 0; k < 8; k++) c = (c & 1) ? 0x82f63b78u ^ (c >> 1) : c >> 1;
     crc32c_tab[n] = c;
   }
 }
+/* once, and complete before any caller reads it: the generator's and the
+ * scan's worker threads all come here first (a thread that saw entry 1 set
+ * while another was still filling the table stored a wrong checksum, and
+ * the engine then refused the block at load) */
+static void crc32c_init(void) { pthread_once(&crc32c_once, crc32c_fill); }
 uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {
   crc32c_init();
   uint64_t crc = 0;
