@@ -494,6 +494,77 @@ int obx_gpu_keyset_host_model(const int64_t *keys, uint64_t n, int kind,
                               const int64_t *probe, uint64_t m, uint8_t *hit,
                               obx_keyset_info *info);
 
+/* ---- key maps: a join's build side with one payload column --------------
+ * The other half of a hash join: a key set drops the probe rows without a
+ * partner, a key map also carries a column of the build side to the probe
+ * side (the reference's ObHashJoinVecOp builds a hash table over the build
+ * rows and probes it per probe row: sql/engine/join/hash_join,
+ * ob_hash_join_vec_op.cpp and its hash_table/). A map lives in device memory,
+ * owned by the context; ids are never reused, and an unknown or freed id
+ * fails with OBX_INVALID_ARGUMENT. Keys are int64 and DISTINCT: a build that
+ * reads a key twice fails with OBX_INVALID_ARGUMENT and keeps nothing (which
+ * payload won would depend on thread order). The payload is one datum of
+ * 1..8 bytes, never NULL, kept widened to 64 bits (sign-extended for numeric
+ * types, zero-extended for char). At most 2^27 keys. Two exact forms
+ * (csrc/obx_keymap.h): dense, payload[key - min] plus a presence bitmap,
+ * when span - 1 < 2 * slots and never past 2^28 entries; else open
+ * addressing over max(64, pow2ceil(2 n)) slots of 16 bytes {key, payload}. */
+#define OBX_COL_JOINED 0xFFF0u   /* the map's payload, as a column of a join scan */
+typedef struct obx_keymap_info {
+  uint64_t n_keys;         /* distinct == read, or the build failed */
+  uint64_t slots_or_span;  /* hash slots, or dense entries */
+  uint64_t bytes;          /* device bytes of the table */
+  int64_t min, max;        /* 1 and -1 when empty */
+  uint8_t kind;            /* 1 hash, 2 dense */
+  uint8_t payload_len, payload_type;
+} obx_keymap_info;
+
+/* n keys and n payload datums of payload->len bytes each, from host memory.
+ * kind: 0 auto, 1 hash, 2 dense. Returns a map id >= 0 or a negative status
+ * (OBX_NOT_SUPPORTED: dense asked for over a span past the cap, or a payload
+ * length outside 1..8). n == 0 is the empty map. */
+int obx_gpu_keymap_create(obx_gpu_ctx *ctx, const int64_t *keys,
+                          const uint8_t *payloads, uint64_t n,
+                          const obx_col_schema *payload, int kind);
+/* The map from position key_idx to position payload_idx of the handle's last
+ * obx_gpu_scan_project result, built on the device from the result's vectors
+ * and null flags. Rows whose key is NULL are skipped; a non-null key with a
+ * NULL payload fails the build with OBX_NOT_SUPPORTED. The result stays
+ * fetchable, unchanged. OBX_INVALID_ARGUMENT if there is no result. */
+int obx_gpu_keymap_from_proj(obx_gpu_ctx *ctx, int handle, uint16_t key_idx,
+                             uint16_t payload_idx, int kind);
+int obx_gpu_keymap_free(obx_gpu_ctx *ctx, int map_id);
+int obx_gpu_keymap_info(obx_gpu_ctx *ctx, int map_id, obx_keymap_info *out);
+/* TEST INFRASTRUCTURE, no HIP call: build the map in host memory with the
+ * same inline functions the device runs, then probe it: hit[i] = 1 iff
+ * probe[i] is a key, and out_payload[i] its payload (u64, widened) where hit.
+ * hit, out_payload and info may be NULL. */
+int obx_gpu_keymap_host_model(const int64_t *keys, const uint8_t *payloads,
+                              uint64_t n, const obx_col_schema *payload,
+                              int kind, const int64_t *probe, uint64_t m,
+                              uint8_t *hit, uint64_t *out_payload,
+                              obx_keymap_info *info);
+
+/* ---- join scan: probe the map in the scan, aggregate the joined rows ----
+ * obx_gpu_scan_filter_agg over the inner join of the table with a map's
+ * build side: a row survives iff the filter passes, probe_col is not NULL and
+ * its value is a key of the map (keys compare as decoded datums, as for
+ * OBX_OP_IN_SET). For a surviving row OBX_COL_JOINED names the payload. It
+ * may stand at either position of agg->group_cols (the key bytes are then
+ * those of a real column of the payload's type and length at that position;
+ * payload length + the other group column's length must be <= 7, else
+ * OBX_NOT_SUPPORTED), and as col_a of COUNT, SUM, MIN or MAX (COUNT(payload)
+ * is COUNT(*): a payload is never NULL). Anywhere else (a filter leaf,
+ * col_b / col_c, the product kinds) it is OBX_INVALID_ARGUMENT. rows_passed
+ * counts joined rows. Results, sorting, the inline limit, paging through
+ * obx_gpu_agg_fetch and OBX_BUF_NOT_ENOUGH are obx_gpu_scan_filter_agg's.
+ * Always the precompiled kernels: obx_gpu_last_jit reports 0. */
+typedef struct obx_join_desc { int32_t map_id; uint16_t probe_col; uint16_t pad; } obx_join_desc;
+int obx_gpu_scan_join_agg(obx_gpu_ctx *ctx, int handle,
+                          const obx_filter_desc *filter,
+                          const obx_join_desc *join, const obx_agg_desc *agg,
+                          obx_agg_result *out);
+
 /* TEST INFRASTRUCTURE: render the hipRTC source the JIT would generate
  * for a plan over a synthetic one-block handle (no GPU needed — codegen
  * and strategy selection are host code). agg == NULL renders the

@@ -23,6 +23,9 @@ OBX_NOT_SUPPORTED = -4007
 
 KS_AUTO, KS_HASH, KS_BITMAP = 0, 1, 2
 
+KM_AUTO, KM_HASH, KM_DENSE = 0, 1, 2
+COL_JOINED = 0xFFF0  # a key map's payload, as a column of a join scan
+
 MAX_GROUPS = 64
 MAX_KEY_BYTES = 16
 
@@ -67,6 +70,20 @@ class KeysetInfo(C.Structure):
     _fields_ = [("n_keys_in", C.c_uint64), ("n_distinct", C.c_uint64),
                 ("slots_or_bits", C.c_uint64), ("bytes", C.c_uint64),
                 ("min", C.c_int64), ("max", C.c_int64), ("kind", C.c_uint8)]
+
+
+class KeymapInfo(C.Structure):
+    """obx_keymap_info: kind 1 = hash, 2 = dense; min > max = empty map."""
+    _fields_ = [("n_keys", C.c_uint64), ("slots_or_span", C.c_uint64),
+                ("bytes", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64),
+                ("kind", C.c_uint8), ("payload_len", C.c_uint8),
+                ("payload_type", C.c_uint8)]
+
+
+class JoinDesc(C.Structure):
+    """obx_join_desc: the map to probe and the column whose value is probed."""
+    _fields_ = [("map_id", C.c_int32), ("probe_col", C.c_uint16),
+                ("pad", C.c_uint16)]
 
 
 class FilterDesc(C.Structure):

@@ -1,8 +1,9 @@
 /*
- * obx_blk.h — the two steps every precompiled generic kernel shares
- * (obx_kernels.hip, obx_project.hip): opening a block and storing a datum.
- * The JIT kernels emit their own forms of both, so this header is not part
- * of the hipRTC compile input.
+ * obx_blk.h — the small steps the precompiled kernels share (obx_kernels.hip,
+ * obx_project.hip, obx_keyset.hip, obx_keymap.hip): opening a block, storing
+ * a datum, and a workgroup sum. The JIT kernels emit their own forms of the
+ * first two and need no workgroup sum, so this header is not part of the
+ * hipRTC compile input.
  */
 #ifndef OBX_BLK_H
 #define OBX_BLK_H
@@ -38,6 +39,18 @@ __device__ __forceinline__ void store_datum(uint8_t *dst, uint64_t uv,
     *(uint32_t *)dst = (uint32_t)uv;
   else
     for (uint32_t i = 0; i < len; i++) dst[i] = (uint8_t)(uv >> (i * 8));
+}
+
+/* sum of one value per thread over the workgroup, valid in thread 0 */
+__device__ __forceinline__ uint64_t wg_sum(uint64_t v) {
+  __shared__ uint64_t part[WAVES];
+  for (int off = 32; off > 0; off >>= 1) v += shflxor64(v, off);
+  __syncthreads(); /* part of a previous call fully read */
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint64_t s = 0;
+  for (uint32_t w = 0; w < WAVES; w++) s += part[w];
+  return s;
 }
 
 #endif /* OBX_BLK_H */

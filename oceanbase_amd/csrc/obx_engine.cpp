@@ -54,6 +54,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->handles.clear(); /* ~obx_handle, while the device is current */
   ctx->keysets.clear();
+  ctx->keymaps.clear();
   (void)hipStreamDestroy(ctx->stream);
   for (hipEvent_t ev : {ctx->ev_start, ctx->ev_stop, ctx->ev_p0, ctx->ev_p1,
                         ctx->ev_mid, ctx->ev_b0, ctx->ev_b1})
@@ -1238,6 +1239,104 @@ extern "C" double obx_gpu_last_proj_stage_ms(obx_gpu_ctx *ctx, int stage) {
   return ctx && stage >= 0 && stage < 3 ? ctx->last_proj_ms[stage] : -1.0;
 }
 
+/* the tail of both aggregate scan verbs: the fetched group table (n_gt
+   slots at gt, its 16 counters at cnt) -> the handle's full sorted group rows
+   (obx_gpu_agg_fetch pages them) and the inline result. key_len is the sum of
+   the group columns' datum lengths. */
+static int table_to_rows(obx_handle &h, const gslot *gt, size_t n_gt,
+                         const unsigned long long *cnt, uint8_t key_len,
+                         const obx_agg_desc *agg, obx_agg_result *out) {
+  /* slots 8..15: striped per-wave survivor sums */
+  unsigned long long passed = cnt[0];
+  for (int i2 = 8; i2 < 16; i2++) passed += cnt[i2];
+
+  memset(out, 0, sizeof(*out));
+  out->rows_scanned = h.total_rows;
+  out->rows_passed = passed;
+  std::vector<const gslot *> live;
+  for (size_t i = 0; i < n_gt; i++)
+    if (gt[i].key != OBX_KEY_EMPTY) live.push_back(&gt[i]);
+  std::sort(live.begin(), live.end(), [](const gslot *a, const gslot *b) {
+    /* little-endian packed keys -> compare as memcmp on key bytes */
+    uint8_t ka[8], kb[8];
+    memcpy(ka, &a->key, 8);
+    memcpy(kb, &b->key, 8);
+    return memcmp(ka, kb, 8) < 0;
+  });
+  /* materialize ALL rows (the growth path's pagination source), then
+     surface the inline result when it fits */
+  h.last_rows.assign(live.size(), obx_group_row());
+  for (size_t i = 0; i < live.size(); i++) {
+    obx_group_row *g = &h.last_rows[i];
+    memcpy(g->key, &live[i]->key, 8);
+    g->key_len = key_len;
+    g->row_count = live[i]->count;
+    uint32_t na = agg ? agg->n_aggs : 0;
+    for (uint32_t a = 0; a < na; a++) {
+      uint8_t kind = agg->aggs[a].kind;
+      if (kind == OBX_AGG_COUNT && agg->aggs[a].col_a == UINT16_MAX) {
+        /* COUNT(*) = the group's row count (group pass) */
+        g->cells[a].limb[0] = live[i]->count;
+        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = 0;
+      } else if (kind == OBX_AGG_MIN || kind == OBX_AGG_MAX) {
+        /* sign-extend the int64 min/max into the 256-bit cell; a group
+           with NO non-null values keeps the init sentinel and its valid
+           flag (cells[a][1]) unset — report 0, matching the oracle's
+           empty-MIN/MAX convention (SQL NULL surfaces via row_count /
+           COUNT(col) at the caller) */
+        int64_t v = live[i]->cells[a][1] ? (int64_t)live[i]->cells[a][0] : 0;
+        g->cells[a].limb[0] = (uint64_t)v;
+        uint64_t s = v < 0 ? ~0ull : 0ull;
+        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = s;
+      } else {
+        for (int l = 0; l < 4; l++)
+          g->cells[a].limb[l] = live[i]->cells[a][l];
+      }
+    }
+  }
+  if (h.last_rows.size() > OBX_MAX_GROUPS) {
+    /* more groups than the inline result holds: rows stay paged behind
+       obx_gpu_agg_fetch (the ObHashGroupByOp growth path) */
+    out->n_groups = (uint32_t)h.last_rows.size();
+    return OBX_BUF_NOT_ENOUGH;
+  }
+  out->n_groups = (uint32_t)h.last_rows.size();
+  for (size_t i = 0; i < h.last_rows.size(); i++)
+    out->groups[i] = h.last_rows[i];
+  return OBX_SUCCESS;
+}
+
+/* the growth path of both aggregate scan verbs: an LDS group table
+   overflowed (counters[1]), so the scan runs again through a direct-global
+   kernel on the OBX_GTABLE_BIG table, which lands in the pinned buffer in
+   place of the small one. launch(table, counters) queues that kernel.
+   AND-only filters: OR-programs keep the capacity error, as do more than
+   OBX_GTABLE_BIG distinct groups (counters[2]). */
+template <class LAUNCH>
+static int rerun_direct(obx_gpu_ctx *ctx, obx_handle &h,
+                        const dev_plan_hdr &ph, uint32_t min_mask,
+                        uint32_t max_mask, size_t *n_gt,
+                        unsigned long long cnt[16], LAUNCH launch) {
+  if (ph.n_prog != 0) return OBX_BUF_NOT_ENOUGH;
+  if (!h.d_gtable_big)
+    HIP_TRY(hipMalloc(&h.d_gtable_big, OBX_RESULT_BYTES(OBX_GTABLE_BIG)));
+  /* same layout as the small table: counters behind the slots */
+  unsigned long long *big_counters =
+      (unsigned long long *)(h.d_gtable_big + OBX_GTABLE_BIG);
+  gtable_init(h.d_gtable_big, OBX_GTABLE_BIG, 16, min_mask, max_mask,
+              ctx->stream);
+  launch(h.d_gtable_big, big_counters);
+  HIP_TRY(hipMemcpyAsync(ctx->h_result, h.d_gtable_big,
+                         OBX_RESULT_BYTES(OBX_GTABLE_BIG),
+                         hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  *n_gt = OBX_GTABLE_BIG;
+  memcpy(cnt, (const gslot *)ctx->h_result + OBX_GTABLE_BIG,
+         16 * sizeof(cnt[0]));
+  if (cnt[2] != 0) return OBX_BUF_NOT_ENOUGH; /* >4096 distinct groups */
+  return OBX_SUCCESS;
+}
+
 extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                                        const obx_filter_desc *filter,
                                        const obx_agg_desc *agg,
@@ -1337,89 +1436,149 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
   memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
   if (cnt[1] != 0) {
     /* a workgroup shard overflowed its LDS group table: rerun with the
-       direct-global high-cardinality kernel (growth path; AND-only
-       filters — OR-programs keep the capacity error) */
-    if (ph.n_prog != 0) return OBX_BUF_NOT_ENOUGH;
-    if (!h.d_gtable_big)
-      HIP_TRY(hipMalloc(&h.d_gtable_big, OBX_RESULT_BYTES(OBX_GTABLE_BIG)));
-    /* same layout as the small table: counters behind the slots */
-    unsigned long long *big_counters =
-        (unsigned long long *)(h.d_gtable_big + OBX_GTABLE_BIG);
-    gtable_init(h.d_gtable_big, OBX_GTABLE_BIG, 16, min_mask, max_mask,
-                ctx->stream);
-    hipLaunchKernelGGL(k_scan_agg_direct, dim3(grid_for(h.n_blocks)),
-                       dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
-                       h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
-                       ph, h.d_gtable_big, big_counters);
-    HIP_TRY(hipMemcpyAsync(ctx->h_result, h.d_gtable_big,
-                           OBX_RESULT_BYTES(OBX_GTABLE_BIG),
-                           hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    n_gt = OBX_GTABLE_BIG;
-    memcpy(cnt, gt + OBX_GTABLE_BIG, sizeof(cnt));
-    if (cnt[2] != 0) return OBX_BUF_NOT_ENOUGH; /* >4096 distinct groups */
+       direct-global high-cardinality kernel */
+    rc = rerun_direct(ctx, h, ph, min_mask, max_mask, &n_gt, cnt,
+                      [&](gslot *big, unsigned long long *big_counters) {
+                        hipLaunchKernelGGL(
+                            k_scan_agg_direct, dim3(grid_for(h.n_blocks)),
+                            dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
+                            h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
+                            ph, big, big_counters);
+                      });
+    if (rc != OBX_SUCCESS) return rc;
   }
-  /* slots 8..15: striped per-wave survivor sums */
-  for (int i2 = 8; i2 < 16; i2++) cnt[0] += cnt[i2];
-
-  memset(out, 0, sizeof(*out));
-  out->rows_scanned = h.total_rows;
-  out->rows_passed = cnt[0];
   uint8_t key_len = 0;
   if (agg)
     for (int g = 0; g < agg->n_group_cols; g++)
       key_len += h.cols[agg->group_cols[g]].len;
-  std::vector<const gslot *> live;
-  for (size_t i = 0; i < n_gt; i++)
-    if (gt[i].key != OBX_KEY_EMPTY) live.push_back(&gt[i]);
-  std::sort(live.begin(), live.end(), [](const gslot *a, const gslot *b) {
-    /* little-endian packed keys -> compare as memcmp on key bytes */
-    uint8_t ka[8], kb[8];
-    memcpy(ka, &a->key, 8);
-    memcpy(kb, &b->key, 8);
-    return memcmp(ka, kb, 8) < 0;
-  });
-  /* materialize ALL rows (the growth path's pagination source), then
-     surface the inline result when it fits */
-  h.last_rows.assign(live.size(), obx_group_row());
-  for (size_t i = 0; i < live.size(); i++) {
-    obx_group_row *g = &h.last_rows[i];
-    memcpy(g->key, &live[i]->key, 8);
-    g->key_len = key_len;
-    g->row_count = live[i]->count;
-    uint32_t na = agg ? agg->n_aggs : 0;
-    for (uint32_t a = 0; a < na; a++) {
-      uint8_t kind = agg->aggs[a].kind;
-      if (kind == OBX_AGG_COUNT && agg->aggs[a].col_a == UINT16_MAX) {
-        /* COUNT(*) = the group's row count (group pass) */
-        g->cells[a].limb[0] = live[i]->count;
-        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = 0;
-      } else if (kind == OBX_AGG_MIN || kind == OBX_AGG_MAX) {
-        /* sign-extend the int64 min/max into the 256-bit cell; a group
-           with NO non-null values keeps the init sentinel and its valid
-           flag (cells[a][1]) unset — report 0, matching the oracle's
-           empty-MIN/MAX convention (SQL NULL surfaces via row_count /
-           COUNT(col) at the caller) */
-        int64_t v = live[i]->cells[a][1] ? (int64_t)live[i]->cells[a][0] : 0;
-        g->cells[a].limb[0] = (uint64_t)v;
-        uint64_t s = v < 0 ? ~0ull : 0ull;
-        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = s;
+  return table_to_rows(h, gt, n_gt, cnt, key_len, agg, out);
+}
+
+/* The join scan: obx_gpu_scan_filter_agg with a key-map probe between the
+   filter and the aggregates (obx_join.hip). The plan never sees
+   OBX_COL_JOINED: prep_query gets the aggregate descriptor with the payload
+   group column removed and COUNT(*) where a payload aggregate stands, and
+   dev_join tells the kernels where the payload goes. */
+extern "C" int obx_gpu_scan_join_agg(obx_gpu_ctx *ctx, int handle,
+                                     const obx_filter_desc *filter,
+                                     const obx_join_desc *join,
+                                     const obx_agg_desc *agg,
+                                     obx_agg_result *out) {
+  obx_handle *hp = obx_handle_lookup(ctx, handle);
+  if (!hp || !out || !join) return OBX_INVALID_ARGUMENT;
+  obx_handle &h = *hp;
+  h.last_rows.clear(); /* no stale pagination after a failed scan */
+  const obx_keymap *km = obx_keymap_lookup(ctx, join->map_id);
+  if (!km || join->probe_col >= h.n_cols) return OBX_INVALID_ARGUMENT;
+  const uint8_t probe_len = h.cols[join->probe_col].len;
+  if (probe_len == 0 || probe_len > 8) return OBX_NOT_SUPPORTED;
+
+  dev_join dj;
+  memset(&dj, 0, sizeof(dj));
+  dj.km = km->view;
+  dj.pay_len = km->info.payload_len;
+  /* plan: what prep_query sees; eff: what the result rows are read by
+     (COUNT(payload) is COUNT(*), a payload is never NULL) */
+  obx_agg_desc plan, eff;
+  memset(&plan, 0, sizeof(plan));
+  memset(&eff, 0, sizeof(eff));
+  uint8_t key_len = 0;
+  if (agg) {
+    if (agg->n_group_cols > 2 || agg->n_aggs > OBX_DEV_MAX_AGGS)
+      return OBX_INVALID_ARGUMENT;
+    eff = *agg;
+    for (int g = 0; g < agg->n_group_cols; g++) {
+      if (agg->group_cols[g] == OBX_COL_JOINED) {
+        if (dj.pay_group) return OBX_INVALID_ARGUMENT; /* named twice */
+        dj.pay_group = 1;
+        dj.pay_pos = (uint8_t)g;
+        key_len += dj.pay_len;
       } else {
-        for (int l = 0; l < 4; l++)
-          g->cells[a].limb[l] = live[i]->cells[a][l];
+        if (agg->group_cols[g] >= h.n_cols) return OBX_INVALID_ARGUMENT;
+        plan.group_cols[plan.n_group_cols++] = agg->group_cols[g];
+        key_len += h.cols[agg->group_cols[g]].len;
+      }
+    }
+    if (dj.pay_group) {
+      dj.real_len = plan.n_group_cols ? h.cols[plan.group_cols[0]].len : 0;
+      if (dj.pay_len + dj.real_len > 7) return OBX_NOT_SUPPORTED;
+    }
+    plan.n_aggs = agg->n_aggs;
+    for (int a = 0; a < agg->n_aggs; a++) {
+      const obx_agg_expr &e = agg->aggs[a];
+      plan.aggs[a] = e;
+      const bool prod = e.kind == OBX_AGG_SUM_PROD2 ||
+                        e.kind == OBX_AGG_SUM_PROD3 ||
+                        e.kind == OBX_AGG_SUM_MUL;
+      if (e.col_b == OBX_COL_JOINED || e.col_c == OBX_COL_JOINED)
+        return OBX_INVALID_ARGUMENT;
+      if (e.col_a != OBX_COL_JOINED) continue;
+      if (prod || e.kind > OBX_AGG_SUM_MUL) return OBX_INVALID_ARGUMENT;
+      plan.aggs[a].kind = OBX_AGG_COUNT; /* neutral: no pass, no operand */
+      plan.aggs[a].col_a = UINT16_MAX;
+      if (e.kind == OBX_AGG_COUNT) {
+        eff.aggs[a].col_a = UINT16_MAX;
+      } else {
+        dj.own_mask |= (uint8_t)(1u << a);
       }
     }
   }
-  if (h.last_rows.size() > OBX_MAX_GROUPS) {
-    /* more groups than the inline result holds: rows stay paged behind
-       obx_gpu_agg_fetch (the ObHashGroupByOp growth path) */
-    out->n_groups = (uint32_t)h.last_rows.size();
-    return OBX_BUF_NOT_ENOUGH;
+
+  HIP_TRY(hipSetDevice(ctx->device));
+  dev_plan_hdr ph;
+  int rc = prep_query(ctx, h, filter, &plan, ph);
+  if (rc != OBX_SUCCESS) return rc;
+  /* the probe column rides in the plan's need slots, so opnd_open reads it
+     like any aggregate operand */
+  uint32_t pi = 0;
+  while (pi < ph.n_need && ph.need_cols[pi] != join->probe_col) pi++;
+  if (pi == ph.n_need) {
+    if (ph.n_need >= OBX_DEV_MAX_NEED) return OBX_NOT_SUPPORTED;
+    ph.need_cols[ph.n_need++] = join->probe_col;
   }
-  out->n_groups = (uint32_t)h.last_rows.size();
-  for (size_t i = 0; i < h.last_rows.size(); i++)
-    out->groups[i] = h.last_rows[i];
-  return OBX_SUCCESS;
+  dj.probe_idx = (uint8_t)pi;
+  for (uint32_t a = 0; a < ph.n_aggs; a++)
+    dj.kind[a] = ((dj.own_mask >> a) & 1) ? agg->aggs[a].kind : ph.aggs[a].kind;
+  ctx->last_jit = 0;
+  ctx->last_grid = 0;
+  ctx->last_bdesc = 0;
+  ctx->bdesc_built = false;
+
+  uint32_t min_mask = 0, max_mask = 0;
+  for (uint32_t a = 0; a < eff.n_aggs; a++) {
+    if (eff.aggs[a].kind == OBX_AGG_MIN) min_mask |= 1u << a;
+    else if (eff.aggs[a].kind == OBX_AGG_MAX) max_mask |= 1u << a;
+  }
+  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, min_mask, max_mask,
+              ctx->stream);
+  HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+  auto kfn = h.lds_ok
+                 ? (ph.n_prog ? k_scan_join_agg_prog_lds : k_scan_join_agg_lds)
+                 : (ph.n_prog ? k_scan_join_agg_prog : k_scan_join_agg);
+  hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+                     ctx->stream, h.d_buf, h.d_blocks, h.n_blocks, h.d_pleaves,
+                     h.d_bleaves, ph, dj, h.d_gtable, h.d_counters);
+  rc = end_timed(ctx, true, h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
+  if (rc != OBX_SUCCESS) return rc;
+
+  const gslot *gt = (const gslot *)ctx->h_result;
+  size_t n_gt = OBX_GTABLE_SLOTS;
+  unsigned long long cnt[16];
+  memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
+  if (cnt[1] != 0) {
+    /* an LDS group table overflowed: the growth path, with the probe */
+    rc = rerun_direct(ctx, h, ph, min_mask, max_mask, &n_gt, cnt,
+                      [&](gslot *big, unsigned long long *big_counters) {
+                        hipLaunchKernelGGL(
+                            k_scan_join_agg_direct,
+                            dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
+                            ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
+                            h.d_pleaves, h.d_bleaves, ph, dj, big,
+                            big_counters);
+                      });
+    if (rc != OBX_SUCCESS) return rc;
+  }
+  return table_to_rows(h, gt, n_gt, cnt, key_len, agg ? &eff : nullptr, out);
 }
 
 extern "C" uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {

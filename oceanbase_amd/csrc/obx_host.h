@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "obx_dev.h"
+#include "obx_keymap.h"
 #include "obx_keyset.h"
 #include "obx_project.h"
 
@@ -112,6 +113,41 @@ extern "C" __global__ void k_keyset_minmax(
 extern "C" __global__ void k_keyset_insert(
     const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint64_t,
     uint64_t *, uint64_t, int64_t, uint32_t, uint32_t, unsigned long long *);
+
+/* key-map build (obx_keymap.hip): as the key-set build, with a payload
+   vector next to the key vector. A row whose key is NULL (bit key_bit of its
+   nulls byte) is skipped. scr words: 0 min, 1 max, 2 non-null keys,
+   3 distinct keys, 4 hash marker flag, 5 the marker's payload, 6 non-null
+   keys whose payload is NULL (bit pay_bit). */
+extern "C" __global__ void k_keymap_minmax(
+    const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint32_t,
+    uint64_t, unsigned long long *);
+extern "C" __global__ void k_keymap_insert(
+    const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint32_t,
+    const uint8_t *, uint32_t, uint64_t, uint64_t *, uint64_t *, uint64_t,
+    int64_t, uint32_t, uint32_t, unsigned long long *);
+
+/* join scan (obx_join.hip): the fused scan kernels with the probe step */
+extern "C" __global__ void k_scan_join_agg(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
+    unsigned long long *);
+extern "C" __global__ void k_scan_join_agg_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
+    unsigned long long *);
+extern "C" __global__ void k_scan_join_agg_prog(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
+    unsigned long long *);
+extern "C" __global__ void k_scan_join_agg_prog_lds(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
+    unsigned long long *);
+extern "C" __global__ void k_scan_join_agg_direct(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
+    unsigned long long *);
 
 #define HIP_TRY(x)                                        \
   do {                                                    \
@@ -266,6 +302,20 @@ struct obx_keyset {
   obx_keyset_info info = {};
 };
 
+/* One device-resident key map (obx_keymap.h): the table and, for the dense
+   form, the presence bitmap behind it in one allocation. Same lifetime rule
+   as a key set. */
+struct obx_keymap {
+  obx_keymap() = default;
+  obx_keymap(const obx_keymap &) = delete;
+  obx_keymap &operator=(const obx_keymap &) = delete;
+  ~obx_keymap() { if (d_table) (void)hipFree(d_table); }
+
+  uint64_t *d_table = nullptr;
+  obx_keymap_dev view = {}; /* what a join scan carries to the kernels */
+  obx_keymap_info info = {};
+};
+
 struct obx_gpu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -289,11 +339,15 @@ struct obx_gpu_ctx {
   std::vector<std::unique_ptr<obx_handle>> handles;
   /* key sets, same rule: a set's id is its index, null once freed */
   std::vector<std::unique_ptr<obx_keyset>> keysets;
+  /* key maps, same rule */
+  std::vector<std::unique_ptr<obx_keymap>> keymaps;
 };
 
 /* every use of a set id resolves it here (obx_keyset.hip): null for a null
    context, an id out of range, or a freed set. No HIP call. */
 const obx_keyset *obx_keyset_lookup(const obx_gpu_ctx *ctx, int64_t set_id);
+/* the same for a map id (obx_keymap.hip) */
+const obx_keymap *obx_keymap_lookup(const obx_gpu_ctx *ctx, int64_t map_id);
 /* every verb resolves its handle id here (obx_engine.cpp): null for a null
    context, an id out of range, or a freed handle */
 obx_handle *obx_handle_lookup(obx_gpu_ctx *ctx, int handle);

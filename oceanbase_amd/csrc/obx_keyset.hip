@@ -23,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "obx_dev_common.h"
+#include "obx_blk.h"
 #include "obx_host.h"
 
 static_assert(sizeof(((dev_leaf *)nullptr)->in_list) >= 5 * sizeof(int64_t),
@@ -31,18 +31,6 @@ static_assert(sizeof(((dev_leaf *)nullptr)->in_list) >= 5 * sizeof(int64_t),
 
 enum { KS_MIN = 0, KS_MAX = 1, KS_COUNT = 2, KS_DISTINCT = 3, KS_MARKER = 4,
        KS_WORDS = 5 };
-
-/* sum of one value per thread over the workgroup, valid in thread 0 */
-__device__ __forceinline__ uint64_t wg_sum(uint64_t v) {
-  __shared__ uint64_t part[WAVES];
-  for (int off = 32; off > 0; off >>= 1) v += shflxor64(v, off);
-  __syncthreads(); /* part of a previous call fully read */
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t s = 0;
-  for (uint32_t w = 0; w < WAVES; w++) s += part[w];
-  return s;
-}
 
 extern "C" __global__ __launch_bounds__(WG) void k_keyset_minmax(
     const uint8_t *__restrict__ src, uint32_t len, uint32_t sign,

@@ -101,6 +101,29 @@ def _load():
     lib.obx_gpu_keyset_host_model.argtypes = [
         C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
         C.POINTER(abi.KeysetInfo)]
+    lib.obx_gpu_keymap_create.restype = C.c_int
+    lib.obx_gpu_keymap_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint64,
+                                          C.POINTER(abi.ColSchema), C.c_int]
+    lib.obx_gpu_keymap_from_proj.restype = C.c_int
+    lib.obx_gpu_keymap_from_proj.argtypes = [C.c_void_p, C.c_int, C.c_uint16,
+                                             C.c_uint16, C.c_int]
+    lib.obx_gpu_keymap_free.restype = C.c_int
+    lib.obx_gpu_keymap_free.argtypes = [C.c_void_p, C.c_int]
+    lib.obx_gpu_keymap_info.restype = C.c_int
+    lib.obx_gpu_keymap_info.argtypes = [C.c_void_p, C.c_int,
+                                        C.POINTER(abi.KeymapInfo)]
+    lib.obx_gpu_keymap_host_model.restype = C.c_int
+    lib.obx_gpu_keymap_host_model.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(abi.ColSchema), C.c_int,
+        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+        C.POINTER(abi.KeymapInfo)]
+    lib.obx_gpu_scan_join_agg.restype = C.c_int
+    lib.obx_gpu_scan_join_agg.argtypes = [C.c_void_p, C.c_int,
+                                          C.POINTER(abi.FilterDesc),
+                                          C.POINTER(abi.JoinDesc),
+                                          C.POINTER(abi.AggDesc),
+                                          C.POINTER(abi.AggResult)]
     for f in ("obx_gpu_total_rows", "obx_gpu_total_bytes",
               "obx_gpu_last_survivors"):
         getattr(lib, f).restype = C.c_uint64
@@ -148,6 +171,53 @@ def keyset_host_model(keys, probe=(), kind=0):
     if rc != 0:
         raise KeysetError("obx_gpu_keyset_host_model", rc)
     return hit.astype(bool), info
+
+
+class KeymapError(RuntimeError):
+    """A key-map or join-scan verb failed; .rc is the engine's status."""
+
+    def __init__(self, what, rc):
+        super().__init__(f"{what} failed: {rc}")
+        self.rc = rc
+
+
+def _payload_args(payloads, spec, n):
+    """(uint8 array of n * len datum bytes, abi.ColSchema) of a payload
+    column. spec = (obj_type, scale, precision, len); payloads is an integer
+    array (the low len bytes of each value are the datum) or an (n, len)
+    uint8 array of datum bytes."""
+    import numpy as np
+    cs = abi.ColSchema(*spec)
+    p = np.asarray(payloads)
+    if p.dtype == np.uint8 and p.ndim == 2:
+        raw = np.ascontiguousarray(p)
+        assert raw.shape == (n, cs.len)
+    else:
+        raw = np.ascontiguousarray(
+            _i64(p).view(np.uint8).reshape(-1, 8)[:, :cs.len])
+        assert raw.shape[0] == n
+    return raw, cs
+
+
+def keymap_host_model(keys, payloads, spec, probe=(), kind=0):
+    """TEST INFRASTRUCTURE: build a key map in host memory with the inline
+    functions the device runs and probe it. Needs no GPU. Returns (hit: bool
+    array over probe, payload: uint64 array, widened, 0 where not hit,
+    abi.KeymapInfo); raises KeymapError with the engine's status."""
+    import numpy as np
+    k, p = _i64(keys), _i64(probe)
+    raw, cs = _payload_args(payloads, spec, k.size)
+    hit = np.zeros(p.size, dtype=np.uint8)
+    pay = np.zeros(p.size, dtype=np.uint64)
+    info = abi.KeymapInfo()
+    rc = lib().obx_gpu_keymap_host_model(
+        k.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p), k.size,
+        C.byref(cs), kind, p.ctypes.data_as(C.c_void_p), p.size,
+        hit.ctypes.data_as(C.c_void_p), pay.ctypes.data_as(C.c_void_p),
+        C.byref(info))
+    if rc != 0:
+        raise KeymapError("obx_gpu_keymap_host_model", rc)
+    return hit.astype(bool), pay, info
 
 
 class GpuEngine:
@@ -224,6 +294,74 @@ class GpuEngine:
         if rc != 0:
             raise KeysetError("obx_gpu_keyset_info", rc)
         return info
+
+    # ---- key maps (a join's build side with one payload column) ----------
+    def keymap_create(self, keys, payloads, spec, kind=0):
+        """Device key map from distinct int64 keys to one payload datum each
+        (see _payload_args for payloads / spec); kind 0 auto, 1 hash,
+        2 dense. Returns the map id a scan_join_agg names."""
+        k = _i64(keys)
+        raw, cs = _payload_args(payloads, spec, k.size)
+        mid = self._lib.obx_gpu_keymap_create(
+            self._ctx, k.ctypes.data_as(C.c_void_p),
+            raw.ctypes.data_as(C.c_void_p), k.size, C.byref(cs), kind)
+        if mid < 0:
+            raise KeymapError("obx_gpu_keymap_create", mid)
+        return mid
+
+    def keymap_from_proj(self, handle, key_idx, payload_idx, kind=0):
+        """Key map from projected position key_idx to position payload_idx
+        of the handle's last scan_project result, built on the device; rows
+        with a NULL key are skipped."""
+        mid = self._lib.obx_gpu_keymap_from_proj(self._ctx, handle, key_idx,
+                                                 payload_idx, kind)
+        if mid < 0:
+            raise KeymapError("obx_gpu_keymap_from_proj", mid)
+        return mid
+
+    def keymap_free(self, mid):
+        rc = self._lib.obx_gpu_keymap_free(self._ctx, mid)
+        if rc != 0:
+            raise KeymapError("obx_gpu_keymap_free", rc)
+
+    def keymap_info(self, mid):
+        info = abi.KeymapInfo()
+        rc = self._lib.obx_gpu_keymap_info(self._ctx, mid, C.byref(info))
+        if rc != 0:
+            raise KeymapError("obx_gpu_keymap_info", rc)
+        return info
+
+    def _scan_join_agg(self, handle, filter_desc, map_id, probe_col,
+                       agg_desc):
+        res = abi.AggResult()
+        join = abi.JoinDesc(map_id, probe_col, 0)
+        rc = self._lib.obx_gpu_scan_join_agg(
+            self._ctx, handle,
+            C.byref(filter_desc) if filter_desc is not None else None,
+            C.byref(join),
+            C.byref(agg_desc) if agg_desc is not None else None,
+            C.byref(res))
+        return rc, res
+
+    def scan_join_agg(self, handle, filter_desc, map_id, probe_col, agg_desc):
+        """scan_filter_agg over the inner join of the table with key map
+        map_id on probe_col; abi.COL_JOINED names the map's payload in
+        agg_desc. Raises KeymapError (with .rc) on any failure."""
+        rc, res = self._scan_join_agg(handle, filter_desc, map_id, probe_col,
+                                      agg_desc)
+        if rc != 0:
+            raise KeymapError("obx_gpu_scan_join_agg", rc)
+        return res
+
+    def scan_join_agg_paged(self, handle, filter_desc, map_id, probe_col,
+                            agg_desc):
+        """The same allowing > OBX_MAX_GROUPS groups: (AggResult, the full
+        sorted row list fetched through obx_gpu_agg_fetch)."""
+        rc, res = self._scan_join_agg(handle, filter_desc, map_id, probe_col,
+                                      agg_desc)
+        if rc not in (0, abi.OBX_BUF_NOT_ENOUGH):
+            raise KeymapError("obx_gpu_scan_join_agg", rc)
+        return res, self.agg_fetch_all(handle)
 
     def filter(self, handle, filter_desc, want_row_ids=False):
         rc = self._lib.obx_gpu_filter(self._ctx, handle,
