@@ -477,15 +477,19 @@ static void jit_v1_merge(const dev_plan_hdr &ph, const jit_shape &js,
        "    uint32_t idx = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - OBX_GTABLE_SHIFT)) "
        "&\n"
        "                   (OBX_GTABLE_SLOTS - 1);\n"
+       "    int found = 0;\n"
        "    for (int probe = 0; probe < OBX_GTABLE_SLOTS; probe++) {\n"
        "      unsigned long long cur_k = atomicCAS(&gtable[idx].key, "
        "OBX_KEY_EMPTY,\n"
        "                                           (unsigned long "
        "long)key);\n"
-       "      if (cur_k == OBX_KEY_EMPTY || cur_k == key) break;\n"
+       "      if (cur_k == OBX_KEY_EMPTY || cur_k == key) { found = 1; "
+       "break; }\n"
        "      idx = (idx + 1) & (OBX_GTABLE_SLOTS - 1);\n"
        "    }\n"
        "    unsigned long long cnt = tab.count[s];\n"
+       "    /* global table full: the growth path, as the spill pass */\n"
+       "    if (!found) { atomicAdd(&counters[1], cnt); continue; }\n"
        "    atomicAdd(&gtable[idx].count, cnt);\n";
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     if (js.agg_wa[a] == 0xFF)

@@ -184,12 +184,15 @@ __device__ __forceinline__ void join_scan_body(
   for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
     uint64_t key = tab.key[s];
     if (key == OBX_KEY_EMPTY) continue;
-    /* a full global table: as in scan_filter_agg_body (known gap) */
-    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
-    const uint32_t idx =
-        gi < 0 ? gtable_home<OBX_GTABLE_SHIFT>(key) : (uint32_t)gi;
     unsigned long long cnt = 0;
     for (uint32_t st = 0; st < OBX_STRIPES; st++) cnt += tab.count[s][st];
+    /* a full global table: the growth path, as in scan_filter_agg_body */
+    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
+    if (gi < 0) {
+      atomicAdd(&counters[1], cnt);
+      continue;
+    }
+    const uint32_t idx = (uint32_t)gi;
     atomicAdd(&gtable[idx].count, cnt);
     for (uint32_t a = 0; a < ph.n_aggs; a++) {
       const bool own = (dj.own_mask >> a) & 1;

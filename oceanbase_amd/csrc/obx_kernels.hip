@@ -195,14 +195,17 @@ __device__ void scan_filter_agg_body(
   for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
     uint64_t key = tab.key[s];
     if (key == OBX_KEY_EMPTY) continue;
-    /* known gap: a full table (more than OBX_GTABLE_SLOTS distinct groups
-       with no workgroup overflowing its LDS table) has no result here; the
-       slot's count and cells then land in the key's home slot */
-    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
-    const uint32_t idx =
-        gi < 0 ? gtable_home<OBX_GTABLE_SHIFT>(key) : (uint32_t)gi;
     unsigned long long cnt = 0;
     for (uint32_t st = 0; st < OBX_STRIPES; st++) cnt += tab.count[s][st];
+    /* a full global table (more than OBX_GTABLE_SLOTS distinct groups, no
+       workgroup past its LDS table): the slot's rows count into counters[1]
+       as an LDS overflow does, and the host takes the growth path */
+    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
+    if (gi < 0) {
+      atomicAdd(&counters[1], cnt);
+      continue;
+    }
+    const uint32_t idx = (uint32_t)gi;
     atomicAdd(&gtable[idx].count, cnt);
     for (uint32_t a = 0; a < ph.n_aggs; a++) {
       uint8_t kind = ph.aggs[a].kind;
