@@ -21,7 +21,7 @@ PYEOF
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
     -Xarch_host -ftrivial-auto-var-init=zero \
     obx_engine.cpp obx_kernels.hip obx_project.hip obx_cs_load.cpp \
-    obx_cs_kernels.hip obx_keyset.hip obx_keymap.hip obx_join.hip \
+    obx_cs_kernels.hip obx_keys.hip obx_join.hip \
     -L/opt/rocm/lib -lhiprtc \
     -o ../libobx.so
 echo "built oceanbase_amd/libobx.so"

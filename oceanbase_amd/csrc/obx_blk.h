@@ -1,6 +1,6 @@
 /*
  * obx_blk.h — the small steps the precompiled kernels share (obx_kernels.hip,
- * obx_project.hip, obx_keyset.hip, obx_keymap.hip): opening a block, storing
+ * obx_project.hip, obx_keys.hip, obx_join.hip): opening a block, storing
  * a datum, and a workgroup sum. The JIT kernels emit their own forms of the
  * first two and need no workgroup sum, so this header is not part of the
  * hipRTC compile input.

@@ -1337,6 +1337,53 @@ static int rerun_direct(obx_gpu_ctx *ctx, obx_handle &h,
   return OBX_SUCCESS;
 }
 
+/* ---- what both aggregate scan verbs run around their own launch ---------- */
+
+/* bit a: cell a is a MIN / a MAX, so the empty group table starts it at its
+   sentinel (k_gtable_init). kind_of(a) is the cell's kind, as in the kernels */
+struct minmax_masks { uint32_t min = 0, max = 0; };
+template <class KIND_OF>
+static minmax_masks agg_minmax_masks(uint32_t n_aggs, KIND_OF kind_of) {
+  minmax_masks m;
+  for (uint32_t a = 0; a < n_aggs; a++) {
+    if (kind_of(a) == OBX_AGG_MIN) m.min |= 1u << a;
+    else if (kind_of(a) == OBX_AGG_MAX) m.max |= 1u << a;
+  }
+  return m;
+}
+
+/* a new scan: what the context reports of the last one starts over */
+static void reset_last_scan(obx_gpu_ctx *ctx) {
+  ctx->last_jit = 0;
+  ctx->last_grid = 0;
+  ctx->last_bdesc = 0;
+  ctx->bdesc_built = false;
+}
+
+/* the tail, after the scan kernel is queued: close the timed region with
+   the copy of table + counters (one allocation, one copy into the pinned
+   buffer), take the growth path when an LDS table overflowed or the global
+   table was full (counters[1]; launch_direct as rerun_direct's launch), and
+   turn the table into rows */
+template <class LAUNCH>
+static int finish_agg_scan(obx_gpu_ctx *ctx, obx_handle &h,
+                           const dev_plan_hdr &ph, minmax_masks mm,
+                           uint8_t key_len, const obx_agg_desc *agg,
+                           obx_agg_result *out, LAUNCH launch_direct) {
+  int rc = end_timed(ctx, true, h.d_gtable,
+                     OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
+  if (rc != OBX_SUCCESS) return rc;
+  const gslot *gt = (const gslot *)ctx->h_result;
+  size_t n_gt = OBX_GTABLE_SLOTS;
+  unsigned long long cnt[16];
+  memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
+  if (cnt[1] != 0) {
+    rc = rerun_direct(ctx, h, ph, mm.min, mm.max, &n_gt, cnt, launch_direct);
+    if (rc != OBX_SUCCESS) return rc;
+  }
+  return table_to_rows(h, gt, n_gt, cnt, key_len, agg, out);
+}
+
 extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                                        const obx_filter_desc *filter,
                                        const obx_agg_desc *agg,
@@ -1350,20 +1397,13 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
   dev_leaf plv[OBX_DEV_MAX_LEAVES];
   int rc = prep_query(ctx, h, filter, agg, ph, plv);
   if (rc != OBX_SUCCESS) return rc;
-  ctx->last_jit = 0;
-  ctx->last_grid = 0;
-  ctx->last_bdesc = 0;
-  ctx->bdesc_built = false;
+  reset_last_scan(ctx);
 
   /* init global table + counters on the device (min/max cells need
      INT64_MAX/MIN) */
-  uint32_t min_mask = 0, max_mask = 0;
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (ph.aggs[a].kind == OBX_AGG_MIN) min_mask |= 1u << a;
-    else if (ph.aggs[a].kind == OBX_AGG_MAX) max_mask |= 1u << a;
-  }
-  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, min_mask, max_mask,
-              ctx->stream);
+  const minmax_masks mm = agg_minmax_masks(
+      ph.n_aggs, [&](uint32_t a) { return ph.aggs[a].kind; });
+  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, mm.min, mm.max, ctx->stream);
 
   /* Default: the fused single-kernel path (measured fastest in round 1).
      OBX_PIPELINE_AGG=1 switches to the filter->group->agg-pass kernel DAG
@@ -1426,32 +1466,19 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                          h.d_counters);
     }
   }
-  /* table + counters are one allocation: one copy into the pinned buffer */
-  rc = end_timed(ctx, true, h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
-  if (rc != OBX_SUCCESS) return rc;
-
-  const gslot *gt = (const gslot *)ctx->h_result;
-  size_t n_gt = OBX_GTABLE_SLOTS;
-  unsigned long long cnt[16];
-  memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
-  if (cnt[1] != 0) {
-    /* a workgroup shard overflowed its LDS group table: rerun with the
-       direct-global high-cardinality kernel */
-    rc = rerun_direct(ctx, h, ph, min_mask, max_mask, &n_gt, cnt,
-                      [&](gslot *big, unsigned long long *big_counters) {
-                        hipLaunchKernelGGL(
-                            k_scan_agg_direct, dim3(grid_for(h.n_blocks)),
-                            dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
-                            h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
-                            ph, big, big_counters);
-                      });
-    if (rc != OBX_SUCCESS) return rc;
-  }
   uint8_t key_len = 0;
   if (agg)
     for (int g = 0; g < agg->n_group_cols; g++)
       key_len += h.cols[agg->group_cols[g]].len;
-  return table_to_rows(h, gt, n_gt, cnt, key_len, agg, out);
+  /* the growth path: the direct-global high-cardinality kernel */
+  return finish_agg_scan(
+      ctx, h, ph, mm, key_len, agg, out,
+      [&](gslot *big, unsigned long long *big_counters) {
+        hipLaunchKernelGGL(k_scan_agg_direct, dim3(grid_for(h.n_blocks)),
+                           dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
+                           h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
+                           ph, big, big_counters);
+      });
 }
 
 /* The join scan: obx_gpu_scan_filter_agg with a key-map probe between the
@@ -1539,18 +1566,12 @@ extern "C" int obx_gpu_scan_join_agg(obx_gpu_ctx *ctx, int handle,
   dj.probe_idx = (uint8_t)pi;
   for (uint32_t a = 0; a < ph.n_aggs; a++)
     dj.kind[a] = ((dj.own_mask >> a) & 1) ? agg->aggs[a].kind : ph.aggs[a].kind;
-  ctx->last_jit = 0;
-  ctx->last_grid = 0;
-  ctx->last_bdesc = 0;
-  ctx->bdesc_built = false;
+  reset_last_scan(ctx);
 
-  uint32_t min_mask = 0, max_mask = 0;
-  for (uint32_t a = 0; a < eff.n_aggs; a++) {
-    if (eff.aggs[a].kind == OBX_AGG_MIN) min_mask |= 1u << a;
-    else if (eff.aggs[a].kind == OBX_AGG_MAX) max_mask |= 1u << a;
-  }
-  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, min_mask, max_mask,
-              ctx->stream);
+  /* by every cell's true kind: the plan holds COUNT(*) for the join's own */
+  const minmax_masks mm = agg_minmax_masks(
+      ph.n_aggs, [&](uint32_t a) { return dj.kind[a]; });
+  gtable_init(h.d_gtable, OBX_GTABLE_SLOTS, 16, mm.min, mm.max, ctx->stream);
   HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
   auto kfn = h.lds_ok
                  ? (ph.n_prog ? k_scan_join_agg_prog_lds : k_scan_join_agg_lds)
@@ -1558,27 +1579,15 @@ extern "C" int obx_gpu_scan_join_agg(obx_gpu_ctx *ctx, int handle,
   hipLaunchKernelGGL(kfn, dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
                      ctx->stream, h.d_buf, h.d_blocks, h.n_blocks, h.d_pleaves,
                      h.d_bleaves, ph, dj, h.d_gtable, h.d_counters);
-  rc = end_timed(ctx, true, h.d_gtable, OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
-  if (rc != OBX_SUCCESS) return rc;
-
-  const gslot *gt = (const gslot *)ctx->h_result;
-  size_t n_gt = OBX_GTABLE_SLOTS;
-  unsigned long long cnt[16];
-  memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
-  if (cnt[1] != 0) {
-    /* an LDS group table overflowed: the growth path, with the probe */
-    rc = rerun_direct(ctx, h, ph, min_mask, max_mask, &n_gt, cnt,
-                      [&](gslot *big, unsigned long long *big_counters) {
-                        hipLaunchKernelGGL(
-                            k_scan_join_agg_direct,
-                            dim3(grid_for(h.n_blocks)), dim3(OBX_WG_HOST), 0,
-                            ctx->stream, h.d_buf, h.d_blocks, h.n_blocks,
-                            h.d_pleaves, h.d_bleaves, ph, dj, big,
-                            big_counters);
-                      });
-    if (rc != OBX_SUCCESS) return rc;
-  }
-  return table_to_rows(h, gt, n_gt, cnt, key_len, agg ? &eff : nullptr, out);
+  /* the growth path, with the probe */
+  return finish_agg_scan(
+      ctx, h, ph, mm, key_len, agg ? &eff : nullptr, out,
+      [&](gslot *big, unsigned long long *big_counters) {
+        hipLaunchKernelGGL(k_scan_join_agg_direct, dim3(grid_for(h.n_blocks)),
+                           dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
+                           h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
+                           ph, dj, big, big_counters);
+      });
 }
 
 extern "C" uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {

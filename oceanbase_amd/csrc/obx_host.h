@@ -104,9 +104,11 @@ extern "C" __global__ void k_project_sel_lds(
 extern "C" __global__ void k_project_pack_nulls(const uint8_t *, uint64_t,
                                                 uint64_t, uint32_t, uint8_t *);
 
-/* key-set build (obx_keyset.hip): keys are the non-null datums of a dense
-   vector of len-byte datums; nulls == nullptr = none are null. scr words:
-   0 min, 1 max, 2 non-null keys, 3 distinct keys, 4 hash marker flag. */
+/* key-set and key-map build (obx_keys.hip): one minmax body and one insert
+   body behind two entries each. Keys are the non-null datums of a dense
+   vector of len-byte datums; nulls == nullptr = none are null. Both builds
+   use one scratch of 7 words; a set's kernels touch the first five: 0 min,
+   1 max, 2 non-null keys, 3 distinct keys, 4 hash marker flag. */
 extern "C" __global__ void k_keyset_minmax(
     const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint64_t,
     unsigned long long *);
@@ -114,11 +116,10 @@ extern "C" __global__ void k_keyset_insert(
     const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint64_t,
     uint64_t *, uint64_t, int64_t, uint32_t, uint32_t, unsigned long long *);
 
-/* key-map build (obx_keymap.hip): as the key-set build, with a payload
-   vector next to the key vector. A row whose key is NULL (bit key_bit of its
-   nulls byte) is skipped. scr words: 0 min, 1 max, 2 non-null keys,
-   3 distinct keys, 4 hash marker flag, 5 the marker's payload, 6 non-null
-   keys whose payload is NULL (bit pay_bit). */
+/* the map's entries: a payload vector next to the key vector. A row whose
+   key is NULL (bit key_bit of its nulls byte) is skipped. Its scratch words
+   go on: 5 the marker's payload, 6 non-null keys whose payload is NULL (bit
+   pay_bit). */
 extern "C" __global__ void k_keymap_minmax(
     const uint8_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint32_t,
     uint64_t, unsigned long long *);
@@ -343,10 +344,10 @@ struct obx_gpu_ctx {
   std::vector<std::unique_ptr<obx_keymap>> keymaps;
 };
 
-/* every use of a set id resolves it here (obx_keyset.hip): null for a null
+/* every use of a set id resolves it here (obx_keys.hip): null for a null
    context, an id out of range, or a freed set. No HIP call. */
 const obx_keyset *obx_keyset_lookup(const obx_gpu_ctx *ctx, int64_t set_id);
-/* the same for a map id (obx_keymap.hip) */
+/* the same for a map id */
 const obx_keymap *obx_keymap_lookup(const obx_gpu_ctx *ctx, int64_t map_id);
 /* every verb resolves its handle id here (obx_engine.cpp): null for a null
    context, an id out of range, or a freed handle */

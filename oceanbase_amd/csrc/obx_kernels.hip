@@ -41,13 +41,20 @@
  *                        gcell_sink
  *   flush_cells<NST>     LDS cell stripes -> global cell
  *   gtable_slot<SHIFT>   global table find-or-insert
+ *   cell_init            a cell's start value for its kind
+ *   lds_table_init / agg_passes / lds_table_flush
+ *                        the fused bodies' LDS group table: start state,
+ *                        phase 3 of a row window (agg_row(lds_sink) per
+ *                        aggregate), the flush (gtable_slot + flush_cells)
+ *   scan_direct_body     the growth path: open + leaf_match + gtable_slot +
+ *                        agg_term(gcell_sink); what a join adds is an argument
  *   store_datum          one VEC_FIXED datum                (obx_blk.h)
- * scan_filter_agg_body = open + filter_window + group_row(lds_slot) +
- * agg_row(lds_sink) + flush_cells; filter_body = open + filter_window +
- * bitmap / row-id output; k_group_pass = open + group_row(gtable_slot);
- * k_agg_pass = open + agg_row(lds_sink) + flush_cells; k_scan_agg_direct =
- * open + gtable_slot + agg_term(gcell_sink); the decode kernels = open +
- * decode_rows.
+ * scan_filter_agg_body = lds_table_init + per window (open + filter_window +
+ * its row count + group_row(lds_slot) + agg_passes) + lds_table_flush;
+ * filter_body = open + filter_window + bitmap / row-id output; k_group_pass =
+ * open + group_row(gtable_slot); k_agg_pass = cell_init + open +
+ * agg_row(lds_sink) + flush_cells; k_scan_agg_direct =
+ * scan_direct_body(no_join); the decode kernels = open + decode_rows.
  */
 #include "obx_steps.h"
 
@@ -74,20 +81,9 @@ __device__ void scan_filter_agg_body(
   const uint32_t lane = tid & 63;
   const uint32_t wv = tid >> 6;
   const uint32_t stripe = lane & (OBX_STRIPES - 1);
+  const auto kind_of = [&](uint32_t a) { return ph.aggs[a].kind; };
 
-  for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
-    tab.key[s] = OBX_KEY_EMPTY;
-    for (uint32_t st = 0; st < OBX_STRIPES; st++) {
-      tab.count[s][st] = 0;
-      for (uint32_t a = 0; a < ph.n_aggs; a++) {
-        uint8_t k = ph.aggs[a].kind;
-        tab.cell[s][a][st][0] = (k == 2) ? (unsigned long long)INT64_MAX
-                                : (k == 3) ? (unsigned long long)INT64_MIN
-                                           : 0ull;
-        tab.cell[s][a][st][1] = 0;
-      }
-    }
-  }
+  lds_table_init(&tab, ph.n_aggs, kind_of);
   if (tid == 0) wg_passed = 0;
   __syncthreads();
 
@@ -141,80 +137,15 @@ __device__ void scan_filter_agg_body(
       }
       __syncthreads();
 
-      /* ---- phase 3: one pass per aggregate (ctxs live one at a time).
-         The kind is a constant of each rows_of instantiation, so its
-         switch stays OUT of the row loop (measured); COUNT(*) needs no
-         pass (filled from tab.count at flush); PROD2+PROD3 with shared
-         inputs run as one fused pass. ---- */
-      for (uint32_t a = 0; a < ph.n_aggs; a++) {
-        const dev_agg ag = ph.aggs[a];
-        if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*) at flush */
-        const bool fuse_p3 = obx_fuse_p3(ph.aggs, ph.n_aggs, a);
-        const dev_agg ag2 = fuse_p3 ? ph.aggs[a + 1] : ag;
-        const agg_opnd oa = opnd_open(ph, cur, ag.ia, blk_bit);
-        const agg_opnd ob = opnd_open(ph, cur, ag.ib, blk_bit);
-        const agg_opnd oc = opnd_open(ph, cur, ag2.ic, blk_bit);
-        auto rows_of = [&](auto kind, auto fuse) {
-          for (uint32_t it = 0; it < iters; it++) {
-            uint32_t rr = it * WG + tid;
-            uint64_t m = pass_bm[it * WAVES + wv];
-            if (!m) continue;
-            bool pass = (m >> lane) & 1;
-            uint8_t slot8 = pass && rr < rows ? u.row_slot[rr] : 255;
-            if (slot8 == 255) continue;
-            agg_row(bv, cur, kind.v, fuse.v != 0, ag, ag2, oa, ob, oc,
-                    w0 + rr,
-                    lds_sink{tab.cell[slot8][a][stripe],
-                             fuse.v ? tab.cell[slot8][a + 1][stripe]
-                                    : nullptr});
-          }
-        };
-        switch (ag.kind) {
-          case 0: rows_of(kc<0>{}, kc<0>{}); break; /* COUNT(col) */
-          case 1: rows_of(kc<1>{}, kc<0>{}); break; /* SUM */
-          case 2: rows_of(kc<2>{}, kc<0>{}); break; /* MIN */
-          case 3: rows_of(kc<3>{}, kc<0>{}); break; /* MAX */
-          case 4: /* SUM_PROD2, optionally with its PROD3 mate */
-            if (fuse_p3) rows_of(kc<4>{}, kc<1>{});
-            else rows_of(kc<4>{}, kc<0>{});
-            break;
-          case 5: rows_of(kc<5>{}, kc<0>{}); break; /* SUM_PROD3 alone */
-          case 6: rows_of(kc<6>{}, kc<0>{}); break; /* SUM_MUL */
-          default: break;
-        }
-        if (fuse_p3) a++; /* consumed the PROD3 mate */
-      }
+      /* ---- phase 3: one pass per aggregate ---- */
+      agg_passes(bv, cur, ph, blk_bit, rows, w0, pass_bm, u.row_slot, &tab);
     }
     __syncthreads(); /* pass_bm reuse across windows */
     } /* window loop */
   }
   __syncthreads();
 
-  /* flush LDS table to the global table (merge lane stripes) */
-  if (tid == 0 && wg_passed) atomicAdd(&counters[0], wg_passed);
-  for (uint32_t s = tid; s < OBX_LTABLE_SLOTS; s += WG) {
-    uint64_t key = tab.key[s];
-    if (key == OBX_KEY_EMPTY) continue;
-    unsigned long long cnt = 0;
-    for (uint32_t st = 0; st < OBX_STRIPES; st++) cnt += tab.count[s][st];
-    /* a full global table (more than OBX_GTABLE_SLOTS distinct groups, no
-       workgroup past its LDS table): the slot's rows count into counters[1]
-       as an LDS overflow does, and the host takes the growth path */
-    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
-    if (gi < 0) {
-      atomicAdd(&counters[1], cnt);
-      continue;
-    }
-    const uint32_t idx = (uint32_t)gi;
-    atomicAdd(&gtable[idx].count, cnt);
-    for (uint32_t a = 0; a < ph.n_aggs; a++) {
-      uint8_t kind = ph.aggs[a].kind;
-      if (kind == 0 && ph.aggs[a].ia == 0xFF) /* COUNT(*): the row count */
-        g_acc_i128(gtable[idx].cells[a], cnt, 0);
-      else
-        flush_cells<OBX_STRIPES>(tab.cell[s][a], kind, gtable[idx].cells[a]);
-    }
-  }
+  lds_table_flush(&tab, &wg_passed, ph, kind_of, gtable, counters);
 }
 
 extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_filter_agg(
@@ -951,9 +882,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_agg_pass(
   for (uint32_t s = tid; s < OBX_GTABLE_SLOTS; s += WG) {
     for (uint32_t f = 0; f < 2; f++) {
       for (uint32_t st = 0; st < 4; st++) {
-        cells[f][s][st][0] = (ag.kind == 2) ? (unsigned long long)INT64_MAX
-                             : (ag.kind == 3) ? (unsigned long long)INT64_MIN
-                                              : 0ull;
+        cells[f][s][st][0] = cell_init(ag.kind);
         cells[f][s][st][1] = 0;
       }
     }
@@ -990,65 +919,16 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_agg_pass(
  * Growth path past the per-workgroup LDS group table (the reference's
  * ObHashGroupByOp hash table grows unboundedly,
  * ob_exec_hash_struct_vec.h:1718): when the generic kernel reports an LDS
- * table overflow, the host reruns the scan with this kernel. No LDS
- * table: every surviving row probes the global group table (open
- * addressing over OBX_GTABLE_BIG) and accumulates with global atomics,
- * each aggregate on its own (no PROD2+PROD3 fusing). Correctness-first
- * slow path — plans that fit the LDS table never take it. AND-combined
- * leaves only (the host keeps OBX_BUF_NOT_ENOUGH for OR-programs). */
+ * table overflow, the host reruns the scan with this kernel
+ * (scan_direct_body, obx_steps.h, with nothing between the filter and the
+ * table). Correctness-first slow path — plans that fit the LDS table never
+ * take it. AND-combined leaves only (the host keeps OBX_BUF_NOT_ENOUGH for
+ * OR-programs). */
 extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
     const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
     gslot *__restrict__ gtable, unsigned long long *__restrict__ counters) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63, wv = tid >> 6;
-  unsigned long long lane_cnt = 0;
-  for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    const dev_block &cur = blocks[b];
-    const blk_leaf *bl = bleaves + (size_t)b * ph.n_leaves;
-    bool skip = false;
-    for (uint32_t i = 0; i < ph.n_leaves; i++)
-      if (leaf_class(cur, plan_leaves[i], bl[i]) == 0) { skip = true; break; }
-    if (skip) continue;
-    const blk_view bv = blk_open<false>(buf, cur, nullptr);
-    const dev_col *gd0 = nullptr, *gd1 = nullptr;
-    if (ph.n_group_cols > 0) gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
-    if (ph.n_group_cols > 1) gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
-    const uint32_t kl0 = ph.group_len[0], kl1 = ph.group_len[1];
-    const uint32_t rows = cur.row_count;
-    for (uint32_t r = tid; r < rows; r += WG) {
-      bool live = true;
-      for (uint32_t i = 0; live && i < ph.n_leaves; i++)
-        live = leaf_match(bv, cur, plan_leaves[i], bl[i], r);
-      if (!live) continue;
-      lane_cnt++;
-      uint64_t key = build_group_key(bv, ph.n_group_cols, gd0, gd1, kl0,
-                                     kl1, r);
-      int gi = gtable_slot<OBX_GTABLE_BIG_SHIFT>(gtable, key);
-      if (gi < 0) { /* global table full: surfaced as counters[2] */
-        atomicAdd(&counters[2], 1ull);
-        continue;
-      }
-      atomicAdd(&gtable[gi].count, 1ull);
-      for (uint32_t a = 0; a < ph.n_aggs; a++) {
-        const dev_agg ag = ph.aggs[a];
-        if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*): count */
-        bool na = false, nb = false, nc = false;
-        int64_t va = 0, vb = 0, vc = 0;
-        if (ag.ia != 0xFF)
-          va = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ia]], r, na);
-        if (ag.kind >= 4 && ag.ib != 0xFF)
-          vb = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ib]], r, nb);
-        if (ag.kind == 5 && ag.ic != 0xFF)
-          vc = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ic]], r, nc);
-        agg_term(ag.kind, false, ag.one_b, ag.one_c, va, na, vb, nb, vc, nc,
-                 gcell_sink{gtable[gi].cells[a]});
-      }
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    lane_cnt += (unsigned long long)__shfl_xor((long long)lane_cnt, off, 64);
-  if (lane == 0 && lane_cnt)
-    atomicAdd(&counters[8 + ((blockIdx.x * WAVES + wv) & 7)], lane_cnt);
+  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph, gtable,
+                   counters, no_join{});
 }

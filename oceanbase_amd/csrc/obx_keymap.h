@@ -1,7 +1,7 @@
 /*
  * obx_keymap.h — device-resident key map: layout and the inline functions
  * that size, fill and probe it, and what a join scan carries to its kernels.
- * Shared by the host engine, the precompiled kernels (obx_keymap.hip,
+ * Shared by the host engine, the precompiled kernels (obx_keys.hip,
  * obx_join.hip) and obx_gpu_keymap_host_model, which runs the very same
  * functions over host memory. No JIT source reads it, so build.sh does not
  * embed it.

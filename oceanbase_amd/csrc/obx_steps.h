@@ -1,9 +1,12 @@
 /*
  * obx_steps.h — the steps the precompiled scan kernels are assembled from
  * (obx_kernels.hip, obx_join.hip): the filter window, grouping, aggregate
- * operands and terms, the LDS and global sinks, the flush and the global
- * group table. Each step exists once; the kernel files hold only the
- * assemblies. Like obx_blk.h, not part of the hipRTC compile input.
+ * operands and terms, the LDS and global sinks, the global group table, the
+ * LDS group table of the fused bodies (start state, the aggregate passes of
+ * a row window, the flush) and the growth-path body. Each step exists once;
+ * the kernel files hold only the assemblies, and obx_join.hip the one step
+ * that is the join's own. Like obx_blk.h, not part of the hipRTC compile
+ * input.
  */
 #ifndef OBX_STEPS_H
 #define OBX_STEPS_H
@@ -362,5 +365,209 @@ __device__ __forceinline__ int gtable_slot(gslot *gt, uint64_t key) {
 
 /* compile-time tag: hands a constant to a generic lambda */
 template <int V> struct kc { static constexpr int v = V; };
+
+/* ---- the per-workgroup LDS group table of the fused scan bodies
+   (scan_filter_agg_body, join_scan_body): its start state, the aggregate
+   passes of one row window, its flush. kind_of(a) is what cell a holds: the
+   plan's kind, or dev_join's where the join step owns cells. ---- */
+
+/* the low word a cell of a kind starts from (the high word starts at 0) */
+__device__ __forceinline__ unsigned long long cell_init(uint8_t kind) {
+  return (kind == 2)   ? (unsigned long long)INT64_MAX  /* MIN */
+         : (kind == 3) ? (unsigned long long)INT64_MIN  /* MAX */
+                       : 0ull;
+}
+
+template <class KIND_OF>
+__device__ __forceinline__ void lds_table_init(lds_table *tab,
+                                               uint32_t n_aggs,
+                                               KIND_OF kind_of) {
+  for (uint32_t s = threadIdx.x; s < OBX_LTABLE_SLOTS; s += WG) {
+    tab->key[s] = OBX_KEY_EMPTY;
+    for (uint32_t st = 0; st < OBX_STRIPES; st++) {
+      tab->count[s][st] = 0;
+      for (uint32_t a = 0; a < n_aggs; a++) {
+        tab->cell[s][a][st][0] = cell_init(kind_of(a));
+        tab->cell[s][a][st][1] = 0;
+      }
+    }
+  }
+}
+
+/* phase 3 of both bodies: one pass per aggregate of the plan over the row
+   window [w0, w0 + rows), reading the pass bitmap and the row -> slot map
+   the earlier phases left (operand ctxs live one at a time). The kind is a
+   constant of each rows_of instantiation, so its switch stays OUT of the row
+   loop (measured); COUNT(*) needs no pass (filled from the row count at
+   flush; a cell the join step owns is COUNT(*) in the plan); PROD2+PROD3
+   with shared inputs run as one fused pass. */
+__device__ __forceinline__ void agg_passes(
+    const blk_view &bv, const dev_block &cur, const dev_plan_hdr &ph,
+    uint64_t blk_bit, uint32_t rows, uint32_t w0, const uint64_t *pass_bm,
+    const uint8_t *row_slot, lds_table *tab) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t stripe = lane & (OBX_STRIPES - 1);
+  const uint32_t iters = (rows + WG - 1) / WG;
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    const dev_agg ag = ph.aggs[a];
+    if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*) at flush */
+    const bool fuse_p3 = obx_fuse_p3(ph.aggs, ph.n_aggs, a);
+    const dev_agg ag2 = fuse_p3 ? ph.aggs[a + 1] : ag;
+    const agg_opnd oa = opnd_open(ph, cur, ag.ia, blk_bit);
+    const agg_opnd ob = opnd_open(ph, cur, ag.ib, blk_bit);
+    const agg_opnd oc = opnd_open(ph, cur, ag2.ic, blk_bit);
+    auto rows_of = [&](auto kind, auto fuse) {
+      for (uint32_t it = 0; it < iters; it++) {
+        uint32_t rr = it * WG + tid;
+        uint64_t m = pass_bm[it * WAVES + wv];
+        if (!m) continue;
+        bool pass = (m >> lane) & 1;
+        uint8_t slot8 = pass && rr < rows ? row_slot[rr] : 255;
+        if (slot8 == 255) continue;
+        agg_row(bv, cur, kind.v, fuse.v != 0, ag, ag2, oa, ob, oc, w0 + rr,
+                lds_sink{tab->cell[slot8][a][stripe],
+                         fuse.v ? tab->cell[slot8][a + 1][stripe] : nullptr});
+      }
+    };
+    switch (ag.kind) {
+      case 0: rows_of(kc<0>{}, kc<0>{}); break; /* COUNT(col) */
+      case 1: rows_of(kc<1>{}, kc<0>{}); break; /* SUM */
+      case 2: rows_of(kc<2>{}, kc<0>{}); break; /* MIN */
+      case 3: rows_of(kc<3>{}, kc<0>{}); break; /* MAX */
+      case 4: /* SUM_PROD2, optionally with its PROD3 mate */
+        if (fuse_p3) rows_of(kc<4>{}, kc<1>{});
+        else rows_of(kc<4>{}, kc<0>{});
+        break;
+      case 5: rows_of(kc<5>{}, kc<0>{}); break; /* SUM_PROD3 alone */
+      case 6: rows_of(kc<6>{}, kc<0>{}); break; /* SUM_MUL */
+      default: break;
+    }
+    if (fuse_p3) a++; /* consumed the PROD3 mate */
+  }
+}
+
+/* the end of both bodies: the workgroup's passed rows into counters[0], then
+   every live slot of the LDS table into the global table (lane stripes
+   merged). A slot without a place in a full global table (more than
+   OBX_GTABLE_SLOTS distinct groups, no workgroup past its LDS table) writes
+   nothing: its rows count into counters[1] as an LDS overflow does, and the
+   host takes the growth path. A COUNT(*) cell is the slot's row count:
+   kind_of(a) == 0 with no operand in the plan decides that for both
+   callers, since the host rewrites COUNT(payload) to COUNT(*) and never
+   marks it in own_mask, while a cell of own_mask holds no operand in the
+   plan but has its own kind in kind_of. */
+template <class KIND_OF>
+__device__ __forceinline__ void lds_table_flush(
+    const lds_table *tab, const unsigned long long *wg_passed,
+    const dev_plan_hdr &ph, KIND_OF kind_of, gslot *__restrict__ gtable,
+    unsigned long long *__restrict__ counters) {
+  if (threadIdx.x == 0 && *wg_passed) atomicAdd(&counters[0], *wg_passed);
+  for (uint32_t s = threadIdx.x; s < OBX_LTABLE_SLOTS; s += WG) {
+    uint64_t key = tab->key[s];
+    if (key == OBX_KEY_EMPTY) continue;
+    unsigned long long cnt = 0;
+    for (uint32_t st = 0; st < OBX_STRIPES; st++) cnt += tab->count[s][st];
+    const int gi = gtable_slot<OBX_GTABLE_SHIFT>(gtable, key);
+    if (gi < 0) {
+      atomicAdd(&counters[1], cnt);
+      continue;
+    }
+    const uint32_t idx = (uint32_t)gi;
+    atomicAdd(&gtable[idx].count, cnt);
+    for (uint32_t a = 0; a < ph.n_aggs; a++) {
+      const uint8_t kind = kind_of(a);
+      if (kind == 0 && ph.aggs[a].ia == 0xFF) /* COUNT(*): the row count */
+        g_acc_i128(gtable[idx].cells[a], cnt, 0);
+      else
+        flush_cells<OBX_STRIPES>(tab->cell[s][a], kind, gtable[idx].cells[a]);
+    }
+  }
+}
+
+/* ---- the growth path: one body for k_scan_agg_direct and
+   k_scan_join_agg_direct. No LDS table: every surviving row resolves its key
+   in the OBX_GTABLE_BIG table (a full table is surfaced as counters[2]) and
+   accumulates with global atomics, each aggregate on its own (no
+   PROD2+PROD3 fusing); the survivor count goes to the striped counters
+   8..15. AND-combined leaves only. `join` is what a join adds between the
+   filter and the table:
+     admit(bv, cur, ph, r, pv)  does row r take part (probe hit)? sets pv
+     key(rk, pv)                the group key from the real columns' key rk
+     own(a, pv, cell)           true when cell a is the join's, accumulated
+   no_join is the plain scan's: every row, the key as built, no cell. ---- */
+struct no_join {
+  __device__ __forceinline__ bool admit(const blk_view &, const dev_block &,
+                                        const dev_plan_hdr &, uint32_t,
+                                        uint64_t &) const { return true; }
+  __device__ __forceinline__ uint64_t key(uint64_t rk, uint64_t) const {
+    return rk;
+  }
+  __device__ __forceinline__ bool own(uint32_t, uint64_t,
+                                      unsigned long long *) const {
+    return false;
+  }
+};
+
+template <class JOIN>
+__device__ __forceinline__ void scan_direct_body(
+    const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
+    uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
+    const blk_leaf *__restrict__ bleaves, const dev_plan_hdr &ph,
+    gslot *__restrict__ gtable, unsigned long long *__restrict__ counters,
+    const JOIN join) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63, wv = tid >> 6;
+  unsigned long long lane_cnt = 0;
+  for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    const dev_block &cur = blocks[b];
+    const blk_leaf *bl = bleaves + (size_t)b * ph.n_leaves;
+    bool skip = false;
+    for (uint32_t i = 0; i < ph.n_leaves; i++)
+      if (leaf_class(cur, plan_leaves[i], bl[i]) == 0) { skip = true; break; }
+    if (skip) continue;
+    const blk_view bv = blk_open<false>(buf, cur, nullptr);
+    const dev_col *gd0 = nullptr, *gd1 = nullptr;
+    if (ph.n_group_cols > 0) gd0 = &cur.cols[ph.need_cols[ph.group_idx[0]]];
+    if (ph.n_group_cols > 1) gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
+    const uint32_t kl0 = ph.group_len[0], kl1 = ph.group_len[1];
+    const uint32_t rows = cur.row_count;
+    for (uint32_t r = tid; r < rows; r += WG) {
+      bool live = true;
+      for (uint32_t i = 0; live && i < ph.n_leaves; i++)
+        live = leaf_match(bv, cur, plan_leaves[i], bl[i], r);
+      if (!live) continue;
+      uint64_t pv = 0;
+      if (!join.admit(bv, cur, ph, r, pv)) continue;
+      lane_cnt++;
+      const uint64_t key = join.key(
+          build_group_key(bv, ph.n_group_cols, gd0, gd1, kl0, kl1, r), pv);
+      int gi = gtable_slot<OBX_GTABLE_BIG_SHIFT>(gtable, key);
+      if (gi < 0) { /* global table full: surfaced as counters[2] */
+        atomicAdd(&counters[2], 1ull);
+        continue;
+      }
+      atomicAdd(&gtable[gi].count, 1ull);
+      for (uint32_t a = 0; a < ph.n_aggs; a++) {
+        if (join.own(a, pv, gtable[gi].cells[a])) continue;
+        const dev_agg ag = ph.aggs[a];
+        if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*): count */
+        bool na = false, nb = false, nc = false;
+        int64_t va = 0, vb = 0, vc = 0;
+        if (ag.ia != 0xFF)
+          va = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ia]], r, na);
+        if (ag.kind >= 4 && ag.ib != 0xFF)
+          vb = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ib]], r, nb);
+        if (ag.kind == 5 && ag.ic != 0xFF)
+          vc = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ic]], r, nc);
+        agg_term(ag.kind, false, ag.one_b, ag.one_c, va, na, vb, nb, vc, nc,
+                 gcell_sink{gtable[gi].cells[a]});
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    lane_cnt += (unsigned long long)__shfl_xor((long long)lane_cnt, off, 64);
+  if (lane == 0 && lane_cnt)
+    atomicAdd(&counters[8 + ((blockIdx.x * WAVES + wv) & 7)], lane_cnt);
+}
 
 #endif /* OBX_STEPS_H */

@@ -222,6 +222,25 @@ MIXED_AGGS = [dict(kind=abi.AGG_COUNT),
               dict(kind=abi.AGG_COUNT, col_a=N)]
 
 
+# every kind through the join scan's aggregate passes and its growth path,
+# OBX_DEV_MAX_AGGS cells: a PROD2 + PROD3 pair over the same a and b (one
+# fused pass; N holds NULLs, so a NULL c drops only the PROD3 half), a PROD3
+# that runs alone, SUM_MUL, MAX and COUNT of the column with NULLs, and one
+# payload aggregate of the join step's own
+ALL_KIND_AGGS = [dict(kind=abi.AGG_COUNT),
+                 dict(kind=abi.AGG_SUM_PROD2, col_a=V, col_b=D),
+                 dict(kind=abi.AGG_SUM_PROD3, col_a=V, col_b=D, col_c=N),
+                 dict(kind=abi.AGG_SUM_PROD3, col_a=V, col_b=N, col_c=D),
+                 dict(kind=abi.AGG_SUM_MUL, col_a=V, col_b=N),
+                 dict(kind=abi.AGG_MAX, col_a=N),
+                 dict(kind=abi.AGG_COUNT, col_a=N),
+                 dict(kind=abi.AGG_SUM, col_a=J)]
+assert len(ALL_KIND_AGGS) == 8   # OBX_DEV_MAX_AGGS
+ALL_KIND_OR = dict(leaves=[dict(col=O, op=abi.OP_LT, lo=5),
+                           dict(col=D, op=abi.OP_GE, lo=6)],
+                   prog=[0, 1, abi.TOK_OR])
+
+
 def run(eng, c, kind, group, aggs, **kw):
     h = eng.load(c.table.bs)
     mid = c.create(eng, kind)
@@ -278,6 +297,40 @@ def test_payload_aggregates_per_real_group(eng):
     run(eng, c, AUTO, [CH], aggs, groups=(3, 3))
     # 20 groups: past the LDS table, so the direct kernel sums the payloads
     run(eng, c, AUTO, [O], aggs, groups=(20, 20))
+
+
+# ---- every aggregate kind through the join scan -------------------------------
+
+@pytest.mark.parametrize("kind", [HASH, DENSE])
+@pytest.mark.parametrize("filt,joined", [({}, 1482), (ALL_KIND_OR, 891)],
+                         ids=["and", "or_prog"])
+def test_all_kinds_staged(eng, filt, joined, kind):
+    """k_scan_join_agg_lds / k_scan_join_agg_prog_lds"""
+    c = staged(pay_kind="int32")
+    assert c.table.total_rows == 2942
+    want = run(eng, c, kind, [CH, J], ALL_KIND_AGGS, groups=(15, 15), **filt)
+    assert want.rows_passed == joined
+
+
+@pytest.mark.parametrize("kind", [HASH, DENSE])
+def test_all_kinds_direct_kernel(eng, kind):
+    """20 groups overflow the LDS table: k_scan_join_agg_direct"""
+    want = run(eng, staged(pay_kind="int32"), kind, [O], ALL_KIND_AGGS,
+               groups=(20, 20))
+    assert want.rows_passed == 1482
+
+
+@pytest.mark.parametrize("kind", [HASH, AUTO])
+@pytest.mark.parametrize("filt,joined", [({}, 2975), (ALL_KIND_OR, 1806)],
+                         ids=["and", "or_prog"])
+def test_all_kinds_unstaged(eng, filt, joined, kind):
+    """k_scan_join_agg / k_scan_join_agg_prog; a dense map cannot span the
+    int64 range"""
+    c = case(tuple(UNSTAGED_BLOCKS), key_kind="raw_fixed", seed=2)
+    assert c.table.total_rows == 6000
+    assert min(c.block_bytes()) > STAGE_BYTES
+    want = run(eng, c, kind, [CH, J], ALL_KIND_AGGS, groups=(15, 15), **filt)
+    assert want.rows_passed == joined
 
 
 # ---- handles, encodings, block verdicts ---------------------------------------
