@@ -428,6 +428,10 @@ int obx_gpu_last_jit(obx_gpu_ctx *ctx);
 /* 1 if that kernel read the handle's packed block descriptors (one
  * 128-byte record per block), 0 if it read the load-time descriptors. */
 int obx_gpu_last_bdesc(obx_gpu_ctx *ctx);
+/* joint-table form of that kernel: 0 none; 1 a weighted joint table; 2 one
+ * axis with the row count packed into each cell; 3 two axes (a table under
+ * 2 KB) with the row count packed in. */
+int obx_gpu_last_joint(obx_gpu_ctx *ctx);
 /* packed descriptor arrays the handle has built so far (a handle caches up
  * to four, one per ordered column list); -1 for an unknown handle. */
 int64_t obx_gpu_bdesc_builds(obx_gpu_ctx *ctx, int handle);

@@ -131,6 +131,15 @@ static uint32_t jit_grid_for(uint32_t n_blocks, uint32_t n_cus, int wpb) {
   return g ? (uint32_t)g : 1;
 }
 
+/* Rows one workgroup of that grid can sweep: its share of the blocks times
+   the rows of the largest block. The bound behind the i64 windows and the
+   row count packed into the joint cells. */
+static uint64_t jit_wg_rows(const obx_handle &h, uint32_t grid) {
+  if (!grid) grid = 1;
+  return (uint64_t)((h.n_blocks + grid - 1) / grid) *
+         (h.max_block_rows ? h.max_block_rows : 4096);
+}
+
 /* device-side fill of an empty group table (EMPTY keys, zero cells, MIN/MAX
    sentinels by aggregate mask) and of the tail_words counters behind it */
 static void gtable_init(gslot *gt, uint32_t n_slots, uint32_t tail_words,
@@ -1357,6 +1366,7 @@ static void reset_last_scan(obx_gpu_ctx *ctx) {
   ctx->last_jit = 0;
   ctx->last_grid = 0;
   ctx->last_bdesc = 0;
+  ctx->last_joint = 0;
   ctx->bdesc_built = false;
 }
 
@@ -1451,6 +1461,7 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
       HIP_TRY(hipEventRecord(ctx->ev_b1, ctx->stream));
     }
     ctx->last_bdesc = bd != nullptr;
+    ctx->last_joint = je ? je->joint : 0;
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     if (je) {
       if (jit_launch(je, h, bd, ctx->stream, &ctx->last_grid) != 0)
@@ -1770,6 +1781,13 @@ extern "C" int obx_gpu_last_jit(obx_gpu_ctx *ctx) {
    (obx_bdesc), 0 if it read dev_block */
 extern "C" int obx_gpu_last_bdesc(obx_gpu_ctx *ctx) {
   return ctx ? ctx->last_bdesc : 0;
+}
+
+/* joint-table form of the last scan's specialized kernel (obx_jit_scan.inc):
+   0 none, 1 weights only, 2 one axis with the row count packed into the
+   cell, 3 two axes (a table under 2 KB) with the row count packed in */
+extern "C" int obx_gpu_last_joint(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->last_joint : 0;
 }
 
 /* how many descriptor arrays this handle has built so far (cache misses) */

@@ -329,6 +329,7 @@ struct obx_gpu_ctx {
   double last_prep_ms = 0.0;  /* plan upload + per-block filter lowering */
   int last_jit = 0;           /* last scan used the specialized kernel */
   int last_bdesc = 0;         /* ... and it read the packed descriptors */
+  int last_joint = 0;         /* ... and its joint-table form (0 = none) */
   /* device times of the last scan_project: filter, block offsets, gather */
   double last_proj_ms[3] = {0.0, 0.0, 0.0};
   uint32_t last_grid = 0;     /* workgroups that kernel was launched with */

@@ -38,7 +38,9 @@
  * environment is read where a strategy is built, and every knob lands in a
  * strategy field that the signature prints:
  *   jit_build_strategy   OBX_JIT_V2 (ok), OBX_JIT_JWS (jws_on, jws_member,
- *                        wa64), OBX_JIT_CTAB (ctab_agg), OBX_JIT_R (r),
+ *                        wa64), OBX_JIT_JPACK (jws_pack, jws_shift, jws_cax,
+ *                        hists),
+ *                        OBX_JIT_CTAB (ctab_agg), OBX_JIT_R (r),
  *                        OBX_JIT_M32 (*_m32), OBX_JIT_STRIPES (stripes),
  *                        OBX_JIT_WPB (wpb), OBX_JIT_BDESC (bdesc),
  *                        OBX_JIT_SGRID via jit_grid_for (decides ok only)
@@ -101,6 +103,7 @@ struct jit_entry {
   int wpb = 0; /* v2: workgroups per CU the launch grid is sized to */
   bool bdesc = false;        /* v2: reads the packed block descriptors ... */
   obx_bdesc_cols bd_cols = {}; /* ... of this ordered column list */
+  int joint = 0;             /* v2: joint-table form (obx_gpu_last_joint) */
 };
 
 struct jit_shape {
@@ -405,6 +408,7 @@ static jit_entry *jit_prepare(const obx_handle &h, const dev_plan_hdr &ph,
   if (je && c.kind == 2) { /* the signature carries both: same for every hit */
     je->bdesc = c.st.bdesc != 0;
     je->bd_cols = c.st.bd_cols;
+    je->joint = jit_joint_form_of(c.st);
   }
   return je;
 }

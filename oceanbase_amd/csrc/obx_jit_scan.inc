@@ -4,7 +4,10 @@
  *
  * Defaults, all measured best (profiles/r02_*, profiles/r03_q1_flush.md):
  * R=4 strip mining, 4 accumulator stripes, single-axis joint histogram
- * unless two axes stay under 2 KB, jcells-sized LDS, striped counter slots,
+ * unless two axes stay under 2 KB, the row count packed into the joint cell
+ * where the weight's bounds allow it (profiles/r10_q1_joint_pack.md;
+ * OBX_JIT_JPACK=0 keeps the count in a histogram of its own), jcells-sized
+ * LDS, striped counter slots,
  * in-workgroup flush reduction, launch grid 8x the resident set
  * (jit_grid_for, obx_engine.cpp — also the grid of the i64 window bound),
  * 32-bit extraction of packed streams with r * width <= 32 (OBX_JIT_M32=0
@@ -156,6 +159,17 @@ struct jit_strategy {
   uint8_t jws_member[OBX_DEV_MAX_AGGS] = {};
   jit_agg_ids jws_f0;                       /* flush factor tab / axis0 */
   jit_agg_ids jws_f1;                       /* flush factor tab / axis1 */
+  /* row count packed into the joint cell: when the weight is proven
+     non-negative, never NULL, and its sum over the rows one workgroup can
+     sweep stays below 2^jws_shift, each row adds weight + (1 << jws_shift),
+     so a cell carries its row count above the weight sum. A joint-axis
+     column then needs no histogram of its own: the aggregates that read
+     one (SUM, COUNT(col), MIN/MAX) take the counts of their axis
+     (jws_cax) at flush, weighted through the ident table jws_ctab */
+  uint8_t jws_pack = 0;
+  uint8_t jws_shift = 0;
+  jit_agg_ids jws_cax;                      /* 0 / 1: counts along that axis */
+  jit_agg_ids jws_ctab;                     /* ident table of that axis col */
   /* narrowed PROD3: when the weight is a CTX column proven in [0, 2^32)
      and both dict factors are proven non-negative with a product below
      2^32, the per-row term is ONE u32 x u32 -> u64 multiply against a
@@ -224,11 +238,17 @@ static int jit_hist_get(jit_strategy &st, uint8_t vc, uint32_t dim) {
   return st.n_hist++;
 }
 
-static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
-                               const jit_shape &js, const dev_leaf *pl,
-                               jit_strategy &st) {
+/* what building a strategy for one joint-table form answered; want_pack =
+   with the row count packed into the joint cell (jit_build_strategy tries
+   that first) */
+enum { JB_OK = 0, JB_NO_V2 = 1, JB_PACK_REFUSED = 2 };
+
+static int jit_build_strategy_form(const obx_handle &h,
+                                   const dev_plan_hdr &ph,
+                                   const jit_shape &js, const dev_leaf *pl,
+                                   bool want_pack, jit_strategy &st) {
   const char *e = getenv("OBX_JIT_V2");
-  if (e && e[0] == '0') return false;
+  if (e && e[0] == '0') return JB_NO_V2;
   /* inline filter: every leaf must be a packed-range-family column
      (k_lower_leaves yields only NONE/ALL/RANGE) or a dict-everywhere
      column (REF_MASK/NONE for every op incl. IN and NU/NN); the whole
@@ -277,7 +297,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   }
   /* persistent group cells need stable group dicts */
   for (uint32_t g2 = 0; g2 < ph.n_group_cols; g2++)
-    if (!h.col_dict_stable[ph.need_cols[ph.group_idx[g2]]]) return false;
+    if (!h.col_dict_stable[ph.need_cols[ph.group_idx[g2]]]) return JB_NO_V2;
   auto maxabs_of = [&](uint8_t need_idx, uint64_t *out) -> bool {
     if (need_idx == 0xFF) return false;
     return jit_col_maxabs(h, ph.need_cols[need_idx], out);
@@ -294,7 +314,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         if (g.ia == 0xFF) { st.astrat[a] = JA_COUNT_STAR; break; }
         if (ja >= 0 && st.vmode[ja] == JV_REF) {
           int hid = jit_hist_get(st, (uint8_t)ja, st.vdim[ja]);
-          if (hid < 0) return false;
+          if (hid < 0) return JB_NO_V2;
           st.astrat[a] = JA_HCOUNT;
           st.ahist[a] = (int8_t)hid;
         } else if (ja >= 0 && !st.vext[ja]) {
@@ -304,18 +324,18 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
           st.wa64[a] = (int8_t)st.n_w64++;
           st.aval_a[a] = (int8_t)ja;
         } else {
-          return false;
+          return JB_NO_V2;
         }
         break;
       case OBX_AGG_SUM:
-        if (ja < 0) return false;
+        if (ja < 0) return JB_NO_V2;
         if (st.vmode[ja] == JV_REF) {
           int hid = jit_hist_get(st, (uint8_t)ja, st.vdim[ja]);
-          if (hid < 0) return false;
+          if (hid < 0) return JB_NO_V2;
           st.astrat[a] = JA_HIST; /* merge multiplies in int128: no bound */
           st.ahist[a] = (int8_t)hid;
         } else {
-          if (!maxabs_of(g.ia, &ma)) return false;
+          if (!maxabs_of(g.ia, &ma)) return JB_NO_V2;
           if (ma > max_term) max_term = ma;
           st.astrat[a] = JA_I64;
           st.wa64[a] = (int8_t)st.n_w64++;
@@ -325,8 +345,8 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
       case OBX_AGG_SUM_PROD2:
       case OBX_AGG_SUM_PROD3:
       case OBX_AGG_SUM_MUL: {
-        if (ja < 0 || jb < 0) return false;
-        if (!maxabs_of(g.ia, &ma) || !maxabs_of(g.ib, &mb)) return false;
+        if (ja < 0 || jb < 0) return JB_NO_V2;
+        if (!maxabs_of(g.ia, &ma) || !maxabs_of(g.ib, &mb)) return JB_NO_V2;
         uint64_t oneb = (uint64_t)(g.one_b < 0 ? -g.one_b : g.one_b);
         uint64_t onec = (uint64_t)(g.one_c < 0 ? -g.one_c : g.one_c);
         uint64_t term;
@@ -335,7 +355,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         } else {
           term = jit_sat_mul(ma, oneb + mb);
           if (g.kind == OBX_AGG_SUM_PROD3) {
-            if (jc < 0 || !maxabs_of(g.ic, &mc)) return false;
+            if (jc < 0 || !maxabs_of(g.ic, &mc)) return JB_NO_V2;
             term = jit_sat_mul(term, onec + mc);
           }
         }
@@ -346,7 +366,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         /* a operand: CTX value, or ident table when the col is dict */
         if (st.vmode[ja] == JV_REF) {
           int t = jit_tab_get(st, (uint8_t)ja, 0, 0, st.vdim[ja]);
-          if (t < 0) return false;
+          if (t < 0) return JB_NO_V2;
           st.atab_a[a] = (int8_t)t;
         }
         /* b operand */
@@ -354,28 +374,28 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
           uint8_t kind = (g.kind == OBX_AGG_SUM_MUL) ? 0 : 1;
           int t = jit_tab_get(st, (uint8_t)jb, kind,
                               kind ? g.one_b : 0, st.vdim[jb]);
-          if (t < 0) return false;
+          if (t < 0) return JB_NO_V2;
           st.atab_b[a] = (int8_t)t;
         }
         if (g.kind == OBX_AGG_SUM_PROD3 && st.vmode[jc] == JV_REF) {
           int t = jit_tab_get(st, (uint8_t)jc, 2, g.one_c, st.vdim[jc]);
-          if (t < 0) return false;
+          if (t < 0) return JB_NO_V2;
           st.atab_c[a] = (int8_t)t;
         }
         break;
       }
       case OBX_AGG_MIN:
       case OBX_AGG_MAX:
-        if (ja < 0) return false;
+        if (ja < 0) return JB_NO_V2;
         if (st.vmode[ja] == JV_REF) {
           /* min/max of a dict column: any live entry bounds it — read it
              off the histogram at flush through the ident table */
           int hid = jit_hist_get(st, (uint8_t)ja, st.vdim[ja]);
-          if (hid < 0) return false;
+          if (hid < 0) return JB_NO_V2;
           st.astrat[a] = JA_HISTMM;
           st.ahist[a] = (int8_t)hid;
           int tt = jit_tab_get(st, (uint8_t)ja, 0, 0, st.vdim[ja]);
-          if (tt < 0) return false;
+          if (tt < 0) return JB_NO_V2;
           st.atab_a[a] = (int8_t)tt;
         } else {
           st.astrat[a] = JA_MM;
@@ -384,9 +404,9 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         }
         break;
       default:
-        return false;
+        return JB_NO_V2;
     }
-    if (st.n_w64 > 8 || st.n_mm > 8) return false;
+    if (st.n_w64 > 8 || st.n_mm > 8) return JB_NO_V2;
   }
 
   /* histogram SUMs read entry weights from an ident table at merge */
@@ -396,7 +416,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     if (st.hist_tab[t2] < 0) {
       int tt = jit_tab_get(st, st.hist_vc[t2], 0, 0,
                            st.vdim[st.hist_vc[t2]]);
-      if (tt < 0) return false;
+      if (tt < 0) return JB_NO_V2;
       st.hist_tab[t2] = (int8_t)tt;
     }
   }
@@ -438,10 +458,26 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
       }
       if (tb[0] >= 0 || tb[1] >= 0) n_axed++;
     }
+    /* packed row count: the preconditions that do not need the grid (the
+       weight is a CTX column here, so vext says whether it can be NULL) */
+    if (want_pack) {
+      bool pack_ok = allow && ok2 && wja >= 0 && !st.vext[wja];
+      if (pack_ok) {
+        const uint16_t wc = js.vcol[wja];
+        pack_ok = h.col_known[wc] && h.col_min[wc] >= 0 &&
+                  h.col_min[wc] <= h.col_max[wc];
+      }
+      if (!pack_ok) return JB_PACK_REFUSED;
+    }
     /* two-axis joint cells cost d0*d1 LDS rows; unless that stays
-       trivial (<2 KB) a single-axis fold is the better trade: members
-       whose factors need the second axis keep their i64 window slot,
-       costing one LDS add per row but a whole occupancy step less */
+       trivial (<2 KB) fold to a single axis: members whose factors need
+       the second axis keep their i64 window slot, one more LDS add per
+       row. Measured on Q1 SF=100 with the row count packed in, where the
+       two-axis table (11.5 KB, 5 workgroups per CU against 7) leaves two
+       LDS atomics per row against three: 2.38 ms per step against 2.26,
+       and the one-axis kernel held to 5 workgroups per CU runs the same
+       2.37 -- the occupancy step costs what the shorter row saves and
+       more (profiles/r10_q1_joint_pack.md) */
     if (allow && axes[1] >= 0) {
       auto adim = [&](int8_t vc) {
         uint32_t d = st.vdim[vc];
@@ -528,6 +564,46 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
         st.n_w64 = nn;
       }
     }
+    if (want_pack && !st.jws_on) return JB_PACK_REFUSED;
+    if (want_pack) {
+      /* a joint-axis column's histogram is a marginal of the packed
+         counts: drop it, and point its aggregates at their axis */
+      st.jws_pack = 1;
+      uint8_t old_vc[4];
+      int8_t old_tab[4], remap[4];
+      const int old_n = st.n_hist;
+      for (int t = 0; t < 4; t++) {
+        old_vc[t] = st.hist_vc[t];
+        old_tab[t] = st.hist_tab[t];
+        remap[t] = -1;
+      }
+      st.n_hist = 0;
+      st.hist_total = 0;
+      for (int t = 0; t < old_n; t++) {
+        if ((int8_t)old_vc[t] == st.jws_a0 || (int8_t)old_vc[t] == st.jws_a1)
+          continue;
+        remap[t] = (int8_t)st.n_hist;
+        st.hist_vc[st.n_hist] = old_vc[t];
+        st.hist_tab[st.n_hist] = old_tab[t];
+        st.hist_off[st.n_hist] = st.hist_total;
+        st.hist_total += st.jcells * st.vdim[old_vc[t]];
+        st.n_hist++;
+      }
+      for (int t = st.n_hist; t < 4; t++) {
+        st.hist_vc[t] = 0;
+        st.hist_tab[t] = 0;
+        st.hist_off[t] = 0;
+      }
+      for (uint32_t a = 0; a < ph.n_aggs; a++) {
+        const int t = st.ahist[a];
+        if (t < 0) continue;
+        st.ahist[a] = remap[t];
+        if (remap[t] >= 0) continue;
+        st.jws_cax[a] = (int8_t)old_vc[t] == st.jws_a0 ? 0 : 1;
+        st.jws_ctab[a] =
+            st.astrat[a] == JA_HISTMM ? st.atab_a[a] : old_tab[t];
+      }
+    }
   }
 
   /* product narrowing (first eligible PROD3 that kept its window slot) */
@@ -606,7 +682,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
 
   /* the persistent-accumulator kernel has no per-block merge: a filter
      that cannot be inlined falls back to the v1 generator */
-  if (ph.n_leaves > 0 && !st.leaf_inline) return false;
+  if (ph.n_leaves > 0 && !st.leaf_inline) return JB_NO_V2;
 
   /* LDS budget: stage buffer (sized to the handle's largest block) +
      persistent shared accumulators */
@@ -635,7 +711,8 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
   lds += 16 * 8 + 16 * 4;                        /* keytab + cslot */
   if (st.jws_on)
     lds += st.jws_cells * st.jws_d0 * st.jws_d1 * 8; /* joint wsum */
-  if (st.cnt_hist < 0) lds += st.jcells * 4 * st.stripes; /* wcnt */
+  if (st.cnt_hist < 0 && !st.jws_pack)
+    lds += st.jcells * 4 * st.stripes; /* wcnt */
   lds += 64;
   st.lds_bytes = lds;
   st.wpb = (int)(163840 / (lds > 1 ? lds : 1));
@@ -645,15 +722,25 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     int w = atoi(we);
     if (w >= 2 && w <= 8 && w < st.wpb) st.wpb = w;
   }
-  if (st.wpb < 2) return false;
+  if (st.wpb < 2) return JB_NO_V2;
   /* i64 window bound over the rows one workgroup sweeps at the launched
      grid (jit_grid_for is what jit_launch uses) */
   {
     const uint32_t grid = jit_grid_for(h.n_blocks, h.n_cus, st.wpb);
-    const uint64_t maxrows =
-        (uint64_t)((h.n_blocks + grid - 1) / grid) *
-        (h.max_block_rows ? h.max_block_rows : 4096);
-    if (jit_sat_mul(max_term, maxrows) >= BOUND) return false;
+    const uint64_t maxrows = jit_wg_rows(h, grid);
+    if (jit_sat_mul(max_term, maxrows) >= BOUND) return JB_NO_V2;
+    /* packed count, over the same rows: the count takes the C bits of
+       maxrows, the weight sum the S = 64 - C below them */
+    if (st.jws_pack) {
+      uint32_t cbits = 0;
+      while (cbits < 64 && (maxrows >> cbits)) cbits++;
+      if (cbits < 1 || cbits > 56) return JB_PACK_REFUSED;
+      const uint32_t sh = 64 - cbits;
+      const unsigned __int128 wsum =
+          (unsigned __int128)(uint64_t)h.col_max[js.vcol[st.jws_ja]] * maxrows;
+      if (wsum >= ((unsigned __int128)1 << sh)) return JB_PACK_REFUSED;
+      st.jws_shift = (uint8_t)sh;
+    }
   }
   /* packed descriptor: off when the column list outgrows the record or a
      listed column has a count or width that does not fit its slot */
@@ -678,7 +765,34 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
     }
   }
   st.ok = true;
-  return true;
+  return JB_OK;
+}
+
+/* The strategy of a plan: with the row count packed into the joint cells
+   where that can be proven, else without. A refused form leaves nothing
+   behind: the other is built from scratch, so it is exactly the strategy
+   OBX_JIT_JPACK=0 gives directly. */
+static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
+                               const jit_shape &js, const dev_leaf *pl,
+                               jit_strategy &st) {
+  const char *pe = getenv("OBX_JIT_JPACK");
+  bool pack = !pe || pe[0] != '0';
+  for (;;) {
+    st = jit_strategy();
+    const int rc = jit_build_strategy_form(h, ph, js, pl, pack, st);
+    if (rc == JB_OK) return true;
+    if (rc != JB_PACK_REFUSED || !pack) break;
+    pack = false;
+  }
+  st = jit_strategy();
+  return false;
+}
+
+/* what obx_gpu_last_joint reports of a strategy */
+static int jit_joint_form_of(const jit_strategy &st) {
+  if (!st.jws_on) return 0;
+  if (!st.jws_pack) return 1;
+  return st.jws_a1 >= 0 ? 3 : 2;
 }
 
 /* every strategy field the generated text reads; per-aggregate entries
@@ -719,6 +833,11 @@ static std::string jit_strategy_sig(const dev_plan_hdr &ph,
     for (uint32_t a = 0; a < ph.n_aggs; a++)
       jit_emit(k, "j%d:%d:%d|", st.jws_member[a], st.jws_f0[a],
                st.jws_f1[a]);
+    if (st.jws_pack) {
+      jit_emit(k, "P%u|", st.jws_shift);
+      for (uint32_t a = 0; a < ph.n_aggs; a++)
+        jit_emit(k, "p%d:%d|", st.jws_cax[a], st.jws_ctab[a]);
+    }
   }
   return k;
 }
@@ -870,10 +989,15 @@ static void jit_v2_prologue(const dev_plan_hdr &ph, const jit_shape &,
 /* LDS declarations and their zeroing */
 static void jit_v2_lds(const dev_plan_hdr &ph, const jit_shape &,
                        const jit_strategy &st, std::string &s) {
+  /* (the packed joint form declares no window array it has no slot for;
+     the other forms keep the one-slot placeholder they always had) */
+  const bool has_w64 = st.n_w64 > 0 || !st.jws_pack;
+  const bool has_wcnt = st.cnt_hist < 0 && !st.jws_pack;
   s += "  __shared__ __attribute__((aligned(16))) uint8_t "
-       "lds_blk[JSTAGE];\n"
-       "  __shared__ unsigned long long wacc64[NW64][JC][NSTRIPE];\n"
-       "  __shared__ uint32_t hist[HTOT];\n";
+       "lds_blk[JSTAGE];\n";
+  if (has_w64)
+    s += "  __shared__ unsigned long long wacc64[NW64][JC][NSTRIPE];\n";
+  s += "  __shared__ uint32_t hist[HTOT];\n";
   if (st.n_mm > 0)
     jit_emit(s,
              "  /* CAS min/max cells: [slot][cell][val, valid] */\n"
@@ -884,7 +1008,7 @@ static void jit_v2_lds(const dev_plan_hdr &ph, const jit_shape &,
   if (st.jws_on)
     jit_emit(s, "  __shared__ unsigned long long jws[%uu * %uu * %uu];\n",
              st.jws_cells, st.jws_d0, st.jws_d1);
-  if (st.cnt_hist < 0)
+  if (has_wcnt)
     s += "  __shared__ uint32_t wcnt[JC][NSTRIPE];\n";
   for (int t = 0; t < st.n_tab; t++)
     jit_emit(s, "  __shared__ long long vt%d[%u];\n", t, st.tabs[t].dim);
@@ -897,9 +1021,10 @@ static void jit_v2_lds(const dev_plan_hdr &ph, const jit_shape &,
        "6;\n"
        "  uint32_t lane_cnt = 0;\n"
        "  const uint32_t stripe = lane & (NSTRIPE - 1);\n"
-       "\n"
-       "  for (uint32_t i = tid; i < NW64 * JC * NSTRIPE; i += WG)\n"
-       "    (&wacc64[0][0][0])[i] = 0;\n";
+       "\n";
+  if (has_w64)
+    s += "  for (uint32_t i = tid; i < NW64 * JC * NSTRIPE; i += WG)\n"
+         "    (&wacc64[0][0][0])[i] = 0;\n";
   /* val slot gets the is_min/is_max sentinel; valid slot 0.  The per-agg
      sentinel depends on kind, so init per (slot,cell). */
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
@@ -918,7 +1043,7 @@ static void jit_v2_lds(const dev_plan_hdr &ph, const jit_shape &,
              "  for (uint32_t i = tid; i < %uu * %uu * %uu; i += WG)\n"
              "    jws[i] = 0;\n",
              st.jws_cells, st.jws_d0, st.jws_d1);
-  if (st.cnt_hist < 0)
+  if (has_wcnt)
     s += "  for (uint32_t i = tid; i < JC * NSTRIPE; i += WG)\n"
          "    (&wcnt[0][0])[i] = 0;\n";
 }
@@ -1191,7 +1316,7 @@ static void jit_v2_accumulate(const dev_plan_hdr &ph, const jit_shape &js,
                               const jit_strategy &st, std::string &s) {
   s += "        lane_cnt += live ? 1u : 0u;\n"
        "        if (live) {\n";
-  if (st.cnt_hist < 0)
+  if (st.cnt_hist < 0 && !st.jws_pack)
     s += "          atomicAdd(&wcnt[cell][stripe], 1u);\n";
   for (int t = 0; t < st.n_hist; t++) {
     const int j = st.hist_vc[t];
@@ -1212,11 +1337,20 @@ static void jit_v2_accumulate(const dev_plan_hdr &ph, const jit_shape &js,
                       axis(st.jws_a1, st.jws_d1).c_str())
             : jit_fmt("cell * %uu + %s", st.jws_d0,
                       axis(st.jws_a0, st.jws_d0).c_str());
-    jit_emit(s,
-             "          if (!nu%1$d)\n"
-             "            atomicAdd(&jws[%2$s],\n"
-             "                      (unsigned long long)v%1$d);\n",
-             st.jws_ja, idx.c_str());
+    if (st.jws_pack)
+      /* weight and row count in one add (the strategy proved the weight
+         sum stays below bit %3$u and the weight is never NULL) */
+      jit_emit(s,
+               "          atomicAdd(&jws[%2$s],\n"
+               "                    (nu%1$d ? 0ull : (unsigned long long)v%1$d) +\n"
+               "                        (1ull << %3$u));\n",
+               st.jws_ja, idx.c_str(), (unsigned)st.jws_shift);
+    else
+      jit_emit(s,
+               "          if (!nu%1$d)\n"
+               "            atomicAdd(&jws[%2$s],\n"
+               "                      (unsigned long long)v%1$d);\n",
+               st.jws_ja, idx.c_str());
   }
   for (uint32_t a = 0; a < ph.n_aggs; a++) {
     const dev_agg &g = ph.aggs[a];
@@ -1441,6 +1575,13 @@ static void jit_v2_flush_cells(const dev_plan_hdr &ph, const jit_shape &,
              "    for (uint32_t ref = 0; ref < %1$uu; ref++)\n"
              "      cnt2 += hist[%2$uu + cell * %1$uu + ref];\n",
              st.vdim[j], st.hist_off[st.cnt_hist]);
+  } else if (st.jws_pack) {
+    /* every live row is in exactly one joint cell of its group cell */
+    jit_emit(s,
+             "    unsigned long long cnt2 = 0;\n"
+             "    for (uint32_t j2 = 0; j2 < %1$uu; j2++)\n"
+             "      cnt2 += jws[cell * %1$uu + j2] >> %2$u;\n",
+             st.jws_d0 * st.jws_d1, (unsigned)st.jws_shift);
   } else {
     s += "    unsigned long long cnt2 = 0;\n"
          "    for (uint32_t s2 = 0; s2 < NSTRIPE; s2++)\n"
@@ -1549,13 +1690,169 @@ static void jit_v2_flush_hists(const dev_plan_hdr &ph, const jit_shape &js,
   }
 }
 
+/* an exact int128 product or sum into a workgroup partial */
+static void jit_v2_emit_facc_i128(std::string &s, int pad,
+                                  const std::string &expr, uint32_t a) {
+  const std::string in(pad, ' ');
+  jit_emit(s,
+           "%1$s{\n"
+           "%1$s  __int128 p = %2$s;\n"
+           "%1$s  if (p != 0) {\n"
+           "%1$s    i128v pv = {(uint64_t)p,\n"
+           "%1$s                (uint64_t)((unsigned __int128)p >> 64)};\n"
+           "%1$s    lds_acc_i128(facc[cell][%3$u], pv);\n"
+           "%1$s  }\n"
+           "%1$s}\n",
+           in.c_str(), expr.c_str(), (unsigned)a);
+}
+
+/* what the two forms of flush pass 3 share: the distinct axis-1 factor
+   tables among the members (each gets an s_c<tab> sum over the d1 ring),
+   and the members' products of a (cell, d0) slice into the partials */
+static int jit_v2_joint_ctabs(const dev_plan_hdr &ph, const jit_strategy &st,
+                              int *c_tabs) {
+  int n_ct = 0;
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (!st.jws_member[a] || st.jws_f1[a] < 0) continue;
+    bool seen = false;
+    for (int q = 0; q < n_ct; q++) seen |= c_tabs[q] == st.jws_f1[a];
+    if (!seen) c_tabs[n_ct++] = st.jws_f1[a];
+  }
+  return n_ct;
+}
+
+static void jit_v2_emit_joint_members(const dev_plan_hdr &ph,
+                                      const jit_strategy &st,
+                                      std::string &s) {
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (!st.jws_member[a]) continue;
+    const int f0 = st.jws_f0[a], f1 = st.jws_f1[a];
+    const std::string sum = f1 >= 0 ? jit_fmt("s_c%d", f1) : "s_pl";
+    jit_v2_emit_facc_i128(
+        s, 6,
+        f0 >= 0   ? jit_fmt("(__int128)vt%d[d0] * %s", f0, sum.c_str())
+        : f1 >= 0 ? sum
+                  : "(__int128)s_pl",
+        a);
+  }
+}
+
+/* flush pass 3 when the joint cells carry the row count (st.jws_pack): a
+   cell splits into its weight sum (low jws_shift bits) and its count. The
+   members take the weights as in the plain form; the aggregates of a
+   joint-axis column (jws_cax) take the counts along their axis, the null
+   bucket excluded as in pass 2. */
+static void jit_v2_flush_joint_packed(const dev_plan_hdr &ph,
+                                      const jit_shape &js,
+                                      const jit_strategy &st,
+                                      std::string &s) {
+  bool ax[2] = {false, false};
+  for (uint32_t a = 0; a < ph.n_aggs; a++)
+    if (st.jws_cax[a] >= 0) ax[st.jws_cax[a]] = true;
+  s += "  {\n";
+  if (ax[0])
+    jit_emit(s, "    const uint32_t hc0 = b0.cols[%u].count;\n",
+             (unsigned)js.vcol[st.jws_a0]);
+  if (ax[1])
+    jit_emit(s, "    const uint32_t hc1 = b0.cols[%u].count;\n",
+             (unsigned)js.vcol[st.jws_a1]);
+  jit_emit(s,
+           "    for (uint32_t idx = tid; idx < fcells * %1$uu; idx += WG) {\n"
+           "      uint32_t cell = idx / %1$uu, d0 = idx %% %1$uu;\n"
+           "      int ce = cslot[cell];\n"
+           "      if (ce < 0) continue;\n"
+           "      long long s_pl = 0;\n"
+           "      unsigned long long n_pl = 0;\n",
+           st.jws_d0);
+  int c_tabs[OBX_DEV_MAX_AGGS];
+  const int n_ct = jit_v2_joint_ctabs(ph, st, c_tabs);
+  for (int q = 0; q < n_ct; q++)
+    jit_emit(s, "      __int128 s_c%d = 0;\n", c_tabs[q]);
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (st.jws_cax[a] != 1) continue;
+    if (st.astrat[a] == JA_HIST)
+      jit_emit(s, "      __int128 h1_%u = 0;\n", (unsigned)a);
+    else if (st.astrat[a] == JA_HCOUNT)
+      jit_emit(s, "      unsigned long long h1_%u = 0;\n", (unsigned)a);
+  }
+  jit_emit(s,
+           "      for (uint32_t d1 = 0; d1 < %1$uu; d1++) {\n"
+           "        const unsigned long long jc =\n"
+           "            jws[cell * %2$uu + d0 * %1$uu + d1];\n"
+           "        if (!jc) continue;\n"
+           "        const long long w = (long long)(jc & ((1ull << %3$u) - 1));\n"
+           "        const unsigned long long c = jc >> %3$u;\n"
+           "        s_pl += w;\n"
+           "        n_pl += c;\n",
+           st.jws_d1, st.jws_d0 * st.jws_d1, (unsigned)st.jws_shift);
+  for (int q = 0; q < n_ct; q++)
+    jit_emit(s, "        s_c%1$d += (__int128)vt%1$d[d1] * w;\n", c_tabs[q]);
+  if (ax[1]) {
+    s += "        if (d1 < hc1) { /* excl. null bucket */\n";
+    for (uint32_t a = 0; a < ph.n_aggs; a++) {
+      if (st.jws_cax[a] != 1) continue;
+      if (st.astrat[a] == JA_HIST)
+        jit_emit(s, "          h1_%u += (__int128)vt%d[d1] * (long long)c;\n",
+                 (unsigned)a, st.jws_ctab[a]);
+      else if (st.astrat[a] == JA_HCOUNT)
+        jit_emit(s, "          h1_%u += c;\n", (unsigned)a);
+      else /* JA_HISTMM: any live entry bounds it */
+        jit_emit(s,
+                 "          cas_minmax(&facc[cell][%1$u][0],\n"
+                 "                     (int64_t)vt%2$d[d1], %3$s);\n"
+                 "          facc[cell][%1$u][1] = 1;\n",
+                 (unsigned)a, st.jws_ctab[a], jit_v2_is_min(ph.aggs[a]));
+    }
+    s += "        }\n";
+  }
+  s += "      }\n"
+       "      if (!n_pl) continue;\n";
+  jit_v2_emit_joint_members(ph, st, s);
+  if (ax[0]) {
+    s += "      if (d0 < hc0) { /* excl. null bucket */\n";
+    for (uint32_t a = 0; a < ph.n_aggs; a++) {
+      if (st.jws_cax[a] != 0) continue;
+      if (st.astrat[a] == JA_HIST)
+        jit_v2_emit_facc_i128(
+            s, 8,
+            jit_fmt("(__int128)vt%d[d0] * (long long)n_pl", st.jws_ctab[a]),
+            a);
+      else if (st.astrat[a] == JA_HCOUNT)
+        jit_emit(s, "        atomicAdd(&facc[cell][%u][0], n_pl);\n",
+                 (unsigned)a);
+      else
+        jit_emit(s,
+                 "        cas_minmax(&facc[cell][%1$u][0],\n"
+                 "                   (int64_t)vt%2$d[d0], %3$s);\n"
+                 "        facc[cell][%1$u][1] = 1;\n",
+                 (unsigned)a, st.jws_ctab[a], jit_v2_is_min(ph.aggs[a]));
+    }
+    s += "      }\n";
+  }
+  for (uint32_t a = 0; a < ph.n_aggs; a++) {
+    if (st.jws_cax[a] != 1) continue;
+    if (st.astrat[a] == JA_HIST)
+      jit_v2_emit_facc_i128(s, 6, jit_fmt("h1_%u", (unsigned)a), a);
+    else if (st.astrat[a] == JA_HCOUNT)
+      jit_emit(s,
+               "      if (h1_%1$u) atomicAdd(&facc[cell][%1$u][0], h1_%1$u);\n",
+               (unsigned)a);
+  }
+  s += "    }\n"
+       "  }\n";
+}
+
 /* flush pass 3: joint weighted cells -> member aggregates. One (cell, d0)
    slice per thread; the d1 ring is reduced in registers, factor products
    applied in int128 (exact: the per-cell i64 bound is enforced at strategy
    build). */
-static void jit_v2_flush_joint(const dev_plan_hdr &ph, const jit_shape &,
+static void jit_v2_flush_joint(const dev_plan_hdr &ph, const jit_shape &js,
                                const jit_strategy &st, std::string &s) {
   if (!st.jws_on) return;
+  if (st.jws_pack) {
+    jit_v2_flush_joint_packed(ph, js, st, s);
+    return;
+  }
   jit_emit(s,
            "  for (uint32_t idx = tid; idx < fcells * %1$uu; idx += WG) "
            "{\n"
@@ -1564,14 +1861,8 @@ static void jit_v2_flush_joint(const dev_plan_hdr &ph, const jit_shape &,
            "    if (ce < 0) continue;\n"
            "    long long s_pl = 0;\n",
            st.jws_d0);
-  /* distinct axis-1 factor tables among members */
-  int c_tabs[OBX_DEV_MAX_AGGS], n_ct = 0;
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (!st.jws_member[a] || st.jws_f1[a] < 0) continue;
-    bool seen = false;
-    for (int q = 0; q < n_ct; q++) seen |= c_tabs[q] == st.jws_f1[a];
-    if (!seen) c_tabs[n_ct++] = st.jws_f1[a];
-  }
+  int c_tabs[OBX_DEV_MAX_AGGS];
+  const int n_ct = jit_v2_joint_ctabs(ph, st, c_tabs);
   for (int q = 0; q < n_ct; q++)
     jit_emit(s, "    __int128 s_c%d = 0;\n", c_tabs[q]);
   jit_emit(s,
@@ -1587,26 +1878,7 @@ static void jit_v2_flush_joint(const dev_plan_hdr &ph, const jit_shape &,
        "    if (s_pl";
   for (int q = 0; q < n_ct; q++) jit_emit(s, " || s_c%d != 0", c_tabs[q]);
   s += ") {\n";
-  for (uint32_t a = 0; a < ph.n_aggs; a++) {
-    if (!st.jws_member[a]) continue;
-    const int f0 = st.jws_f0[a], f1 = st.jws_f1[a];
-    const std::string sum = f1 >= 0 ? jit_fmt("s_c%d", f1) : "s_pl";
-    const std::string expr =
-        f0 >= 0   ? jit_fmt("(__int128)vt%d[d0] * %s", f0, sum.c_str())
-        : f1 >= 0 ? sum
-                  : "(__int128)s_pl";
-    jit_emit(s,
-             "      {\n"
-             "        __int128 p = %s;\n"
-             "        if (p != 0) {\n"
-             "          i128v pv = {(uint64_t)p,\n"
-             "                      (uint64_t)((unsigned __int128)p >> "
-             "64)};\n"
-             "          lds_acc_i128(facc[cell][%u], pv);\n"
-             "        }\n"
-             "      }\n",
-             expr.c_str(), (unsigned)a);
-  }
+  jit_v2_emit_joint_members(ph, st, s);
   s += "    }\n"
        "  }\n";
 }

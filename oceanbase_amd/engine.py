@@ -84,6 +84,8 @@ def _load():
     lib.obx_gpu_last_jit.argtypes = [C.c_void_p]
     lib.obx_gpu_last_bdesc.restype = C.c_int
     lib.obx_gpu_last_bdesc.argtypes = [C.c_void_p]
+    lib.obx_gpu_last_joint.restype = C.c_int
+    lib.obx_gpu_last_joint.argtypes = [C.c_void_p]
     lib.obx_gpu_bdesc_builds.restype = C.c_int64
     lib.obx_gpu_bdesc_builds.argtypes = [C.c_void_p, C.c_int]
     lib.obx_gpu_keyset_create.restype = C.c_int
@@ -538,6 +540,12 @@ class GpuEngine:
     def last_jit(self):
         """True if the last scan ran the hipRTC plan-specialized kernel."""
         return bool(self._lib.obx_gpu_last_jit(self._ctx))
+
+    def last_joint(self):
+        """Joint-table form of the last scan's specialized kernel: 0 none,
+        1 weights only, 2 one axis with the row count packed into the cell,
+        3 two axes (a table under 2 KB) with the row count packed in."""
+        return int(self._lib.obx_gpu_last_joint(self._ctx))
 
     def last_prep_ms(self):
         """Device time of the last query's prep (plan upload + per-block

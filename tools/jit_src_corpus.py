@@ -25,7 +25,7 @@ from test_scan_flush_source import _lib, _lineitem_summaries, _q1  # noqa: E402
 KNOBS = ("OBX_JIT_R", "OBX_JIT_STRIPES", "OBX_JIT_M32", "OBX_JIT_CTAB",
          "OBX_JIT_JWS", "OBX_JIT_BDESC", "OBX_JIT_WPB", "OBX_JIT_V2",
          "OBX_JIT_FSTAGE", "OBX_JIT_FR", "OBX_JIT_FU", "OBX_JIT_FSL",
-         "OBX_DUMP_RID", "OBX_JIT_SGRID")
+         "OBX_DUMP_RID", "OBX_JIT_SGRID", "OBX_JIT_JPACK")
 
 # column facts of obx_jit_dump_src_ex: 1 dict in every block, 2 may be NULL,
 # 4 bounds known, 8 aligned 8-byte RAW, 16 packed-range family, 32 dict stable
@@ -121,6 +121,16 @@ def scan_cases():
                  ("CTAB", "0"), ("JWS", "0"), ("BDESC", "0"), ("WPB", "3"),
                  ("V2", "0")):
         yield "q1_%s%s" % (k.lower(), v), q1f, q1a, li2, {}, {"OBX_JIT_" + k: v}
+    # joint-table forms: one axis with the packed row count (q1_grid), the
+    # same without it, both axes with it (q1_nogroup: 12 x 10 cells) and
+    # without; a workgroup with so many rows that the count cannot be packed
+    yield "q1_grid_jpack0", q1f, q1a, li2, dict(n_blocks=453858, n_cus=256), \
+        dict(OBX_JIT_JPACK="0")
+    yield "q1_grid_sgrid64", q1f, q1a, li2, dict(n_blocks=453858, n_cus=256), \
+        dict(OBX_JIT_SGRID="64")
+    yield "q1_nogroup_jpack0", q1f, A.make_agg([], [
+        CNT, SUM(0), SUM(1), P2(1, 2), P3(1, 2, 3), SUM(2)]), table(), {}, \
+        dict(OBX_JIT_JPACK="0")
     yield "q1_v1_wpb5", q1f, q1a, li(), {}, dict(OBX_JIT_V2="0",
                                                  OBX_JIT_WPB="5")
     yield "q1_force_v1", q1f, q1a, li(), dict(force_v1=1), {}
