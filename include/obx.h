@@ -448,13 +448,42 @@ uint64_t obx_gpu_last_survivors(obx_gpu_ctx *ctx, int handle);
  * (ob_exec_hash_struct_vec.h:1718); here a scan whose group count
  * exceeds OBX_MAX_GROUPS returns OBX_BUF_NOT_ENOUGH with
  * obx_agg_result.n_groups set to the true total, and the rows (sorted
- * by key bytes) are fetched in pages. Device capacity: OBX_GTABLE_BIG
- * (4096) distinct groups; the engine transparently reruns an
- * LDS-table-overflowed generic scan through a direct-global
- * high-cardinality kernel (AND-combined filters only). */
+ * by key bytes) are fetched in pages. Device capacity: the context's cap,
+ * obx_gpu_set_max_groups below, by default OBX_GTABLE_BIG (4096) distinct
+ * groups; the engine transparently reruns an LDS-table-overflowed generic
+ * scan through a direct-global high-cardinality kernel (AND-combined
+ * filters only), on a fixed 4096-slot table at the default cap and on a
+ * hash table sized from the cap above it. */
 int obx_gpu_agg_fetch(obx_gpu_ctx *ctx, int handle, uint32_t start,
                       uint32_t count, obx_group_row *out, uint32_t *n_out,
                       uint64_t *n_total);
+/* most distinct groups a scan of this context may produce. Default and
+ * minimum 4096 (OBX_GTABLE_BIG: behaviour as before). Above it, a scan whose
+ * LDS tables overflow runs on a hash table in device memory sized from
+ * this cap (16 + 32 * n_aggs bytes per slot, at least 2 slots per granted
+ * group). A scan succeeds iff its distinct groups <= max_groups, whatever
+ * the order of the rows; one that does not returns OBX_BUF_NOT_ENOUGH in
+ * bounded time and leaves nothing to fetch. < 4096: OBX_INVALID_ARGUMENT;
+ * > 2^24: OBX_NOT_SUPPORTED. */
+int obx_gpu_set_max_groups(obx_gpu_ctx *ctx, uint64_t max_groups);
+uint64_t obx_gpu_max_groups(obx_gpu_ctx *ctx);
+/* slots of the sized table the last aggregate scan ran on; 0 when it did
+ * not need one (under a raised cap every scan whose LDS tables overflowed
+ * needs one, however few groups it has) */
+uint64_t obx_gpu_last_group_slots(obx_gpu_ctx *ctx);
+/* device time of that table's scan kernel, ms; 0 when none ran */
+double obx_gpu_last_group_ms(obx_gpu_ctx *ctx);
+/* TEST INFRASTRUCTURE, no HIP call: the sized table over host memory, by the
+ * sizing and find-or-insert functions the kernels run (csrc/obx_grouphash.h).
+ * n u64 keys inserted in order under max_groups; the stop word is looked at
+ * every in_flight keys. Returns OBX_SUCCESS or OBX_BUF_NOT_ENOUGH as the
+ * scan would, and the table's slots, live keys, longest probe sequence,
+ * input keys found again, and bytes at n_aggs aggregates. */
+int obx_gpu_group_hash_host_model(const uint64_t *keys, uint64_t n,
+                                  uint64_t max_groups, uint64_t in_flight,
+                                  uint32_t n_aggs, uint64_t *slots,
+                                  uint64_t *live, uint64_t *max_probe,
+                                  uint64_t *found, uint64_t *bytes);
 /* CPU-oracle mirror (test infrastructure) */
 int obx_cpu_agg_fetch(uint32_t start, uint32_t count, obx_group_row *out,
                       uint32_t *n_out, uint64_t *n_total);

@@ -27,6 +27,12 @@ KM_AUTO, KM_HASH, KM_DENSE = 0, 1, 2
 COL_JOINED = 0xFFF0  # a key map's payload, as a column of a join scan
 
 MAX_GROUPS = 64
+# the cap on a scan's distinct groups (obx_gpu_set_max_groups): its default
+# and minimum (OBX_GTABLE_BIG), the most a caller may grant, and the sized
+# table's smallest slot count
+GROUP_CAP_DEFAULT = 4096
+GROUP_CAP_MAX = 1 << 24
+GROUP_HASH_MIN_SLOTS = 1 << 13
 MAX_KEY_BYTES = 16
 
 

@@ -69,7 +69,7 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
    them, hold only nulls and make no HIP call. */
 obx_handle::~obx_handle() {
   void *owned[] = {d_buf, d_blocks, d_bleaves, d_pleaves, d_gtable,
-                   d_gtable_big, d_proj_scratch, d_bitmap, d_row_ids,
+                   d_gtable_big, d_ghash, d_grecs, d_proj_scratch, d_bitmap, d_row_ids,
                    d_blk_counts, d_row_slot, d_minmax, d_sel_nulls,
                    d_sel_row_nos, d_blk_off, d_tile_sums, d_sel_bits};
   for (void *p : owned)
@@ -1248,13 +1248,51 @@ extern "C" double obx_gpu_last_proj_stage_ms(obx_gpu_ctx *ctx, int stage) {
   return ctx && stage >= 0 && stage < 3 ? ctx->last_proj_ms[stage] : -1.0;
 }
 
-/* the tail of both aggregate scan verbs: the fetched group table (n_gt
-   slots at gt, its 16 counters at cnt) -> the handle's full sorted group rows
+/* one live group as either table hands it over: a gslot of the fixed
+   tables, or a compacted record of the sized one. cells = n_aggs x 4 limbs */
+struct live_group {
+  uint64_t key, count;
+  const unsigned long long *cells;
+};
+
+/* one group -> its result row: COUNT(*) from the row count, MIN/MAX sign
+   extension and the "no value seen" rule, everything else limb by limb */
+static void group_to_row(const live_group &lg, uint8_t key_len,
+                         const obx_agg_desc *agg, obx_group_row *g) {
+  memcpy(g->key, &lg.key, 8);
+  g->key_len = key_len;
+  g->row_count = lg.count;
+  uint32_t na = agg ? agg->n_aggs : 0;
+  for (uint32_t a = 0; a < na; a++) {
+    const unsigned long long *cell = lg.cells + 4 * a;
+    uint8_t kind = agg->aggs[a].kind;
+    if (kind == OBX_AGG_COUNT && agg->aggs[a].col_a == UINT16_MAX) {
+      /* COUNT(*) = the group's row count (group pass) */
+      g->cells[a].limb[0] = lg.count;
+      g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = 0;
+    } else if (kind == OBX_AGG_MIN || kind == OBX_AGG_MAX) {
+      /* sign-extend the int64 min/max into the 256-bit cell; a group
+         with NO non-null values keeps the init sentinel and its valid
+         flag (cell[1]) unset — report 0, matching the oracle's
+         empty-MIN/MAX convention (SQL NULL surfaces via row_count /
+         COUNT(col) at the caller) */
+      int64_t v = cell[1] ? (int64_t)cell[0] : 0;
+      g->cells[a].limb[0] = (uint64_t)v;
+      uint64_t s = v < 0 ? ~0ull : 0ull;
+      g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = s;
+    } else {
+      for (int l = 0; l < 4; l++) g->cells[a].limb[l] = cell[l];
+    }
+  }
+}
+
+/* the tail of both aggregate scan verbs: the live groups (in any order) and
+   the scan's 16 counters at cnt -> the handle's full sorted group rows
    (obx_gpu_agg_fetch pages them) and the inline result. key_len is the sum of
    the group columns' datum lengths. */
-static int table_to_rows(obx_handle &h, const gslot *gt, size_t n_gt,
-                         const unsigned long long *cnt, uint8_t key_len,
-                         const obx_agg_desc *agg, obx_agg_result *out) {
+static int groups_to_rows(obx_handle &h, std::vector<live_group> &live,
+                          const unsigned long long *cnt, uint8_t key_len,
+                          const obx_agg_desc *agg, obx_agg_result *out) {
   /* slots 8..15: striped per-wave survivor sums */
   unsigned long long passed = cnt[0];
   for (int i2 = 8; i2 < 16; i2++) passed += cnt[i2];
@@ -1262,47 +1300,19 @@ static int table_to_rows(obx_handle &h, const gslot *gt, size_t n_gt,
   memset(out, 0, sizeof(*out));
   out->rows_scanned = h.total_rows;
   out->rows_passed = passed;
-  std::vector<const gslot *> live;
-  for (size_t i = 0; i < n_gt; i++)
-    if (gt[i].key != OBX_KEY_EMPTY) live.push_back(&gt[i]);
-  std::sort(live.begin(), live.end(), [](const gslot *a, const gslot *b) {
+  std::sort(live.begin(), live.end(),
+            [](const live_group &a, const live_group &b) {
     /* little-endian packed keys -> compare as memcmp on key bytes */
     uint8_t ka[8], kb[8];
-    memcpy(ka, &a->key, 8);
-    memcpy(kb, &b->key, 8);
+    memcpy(ka, &a.key, 8);
+    memcpy(kb, &b.key, 8);
     return memcmp(ka, kb, 8) < 0;
   });
   /* materialize ALL rows (the growth path's pagination source), then
      surface the inline result when it fits */
   h.last_rows.assign(live.size(), obx_group_row());
-  for (size_t i = 0; i < live.size(); i++) {
-    obx_group_row *g = &h.last_rows[i];
-    memcpy(g->key, &live[i]->key, 8);
-    g->key_len = key_len;
-    g->row_count = live[i]->count;
-    uint32_t na = agg ? agg->n_aggs : 0;
-    for (uint32_t a = 0; a < na; a++) {
-      uint8_t kind = agg->aggs[a].kind;
-      if (kind == OBX_AGG_COUNT && agg->aggs[a].col_a == UINT16_MAX) {
-        /* COUNT(*) = the group's row count (group pass) */
-        g->cells[a].limb[0] = live[i]->count;
-        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = 0;
-      } else if (kind == OBX_AGG_MIN || kind == OBX_AGG_MAX) {
-        /* sign-extend the int64 min/max into the 256-bit cell; a group
-           with NO non-null values keeps the init sentinel and its valid
-           flag (cells[a][1]) unset — report 0, matching the oracle's
-           empty-MIN/MAX convention (SQL NULL surfaces via row_count /
-           COUNT(col) at the caller) */
-        int64_t v = live[i]->cells[a][1] ? (int64_t)live[i]->cells[a][0] : 0;
-        g->cells[a].limb[0] = (uint64_t)v;
-        uint64_t s = v < 0 ? ~0ull : 0ull;
-        g->cells[a].limb[1] = g->cells[a].limb[2] = g->cells[a].limb[3] = s;
-      } else {
-        for (int l = 0; l < 4; l++)
-          g->cells[a].limb[l] = live[i]->cells[a][l];
-      }
-    }
-  }
+  for (size_t i = 0; i < live.size(); i++)
+    group_to_row(live[i], key_len, agg, &h.last_rows[i]);
   if (h.last_rows.size() > OBX_MAX_GROUPS) {
     /* more groups than the inline result holds: rows stay paged behind
        obx_gpu_agg_fetch (the ObHashGroupByOp growth path) */
@@ -1313,6 +1323,17 @@ static int table_to_rows(obx_handle &h, const gslot *gt, size_t n_gt,
   for (size_t i = 0; i < h.last_rows.size(); i++)
     out->groups[i] = h.last_rows[i];
   return OBX_SUCCESS;
+}
+
+/* ... from a fetched table of n_gt gslots */
+static int table_to_rows(obx_handle &h, const gslot *gt, size_t n_gt,
+                         const unsigned long long *cnt, uint8_t key_len,
+                         const obx_agg_desc *agg, obx_agg_result *out) {
+  std::vector<live_group> live;
+  for (size_t i = 0; i < n_gt; i++)
+    if (gt[i].key != OBX_KEY_EMPTY)
+      live.push_back({gt[i].key, gt[i].count, &gt[i].cells[0][0]});
+  return groups_to_rows(h, live, cnt, key_len, agg, out);
 }
 
 /* the growth path of both aggregate scan verbs: an LDS group table
@@ -1348,6 +1369,82 @@ static int rerun_direct(obx_gpu_ctx *ctx, obx_handle &h,
 
 /* ---- what both aggregate scan verbs run around their own launch ---------- */
 
+/* rows all workgroups of a sized-table scan together may insert between two
+   looks at the stop word: each looks once per block */
+static uint64_t group_hash_in_flight(const obx_handle &h) {
+  return (uint64_t)grid_for(h.n_blocks) *
+         (h.max_block_rows ? h.max_block_rows : 4096);
+}
+
+/* the growth path under a raised cap (obx_gpu_set_max_groups): an LDS group
+   table overflowed (counters[1]), so the scan runs again on a hash table in
+   device memory sized from the cap (obx_grouphash.h); launch(table,
+   max_groups, counters) queues that kernel. The bound on the survivors is
+   the table's row count: the first kernel's counters are not a count of
+   survivors once a table overflowed. The counter block comes back first:
+   its winner words are the live keys, which decide the refusal and size the
+   compacted records; then k_group_compact and one copy of exactly those
+   records. A refused scan has not seen every row, so nothing of it is
+   reported. */
+template <class LAUNCH>
+static int rerun_hash(obx_gpu_ctx *ctx, obx_handle &h, const dev_plan_hdr &ph,
+                      uint32_t min_mask, uint32_t max_mask, uint8_t key_len,
+                      const obx_agg_desc *agg, obx_agg_result *out,
+                      LAUNCH launch) {
+  if (ph.n_prog != 0) return OBX_BUF_NOT_ENOUGH;
+  const uint64_t slots =
+      obx_gh_slots(ctx->max_groups, h.total_rows, group_hash_in_flight(h));
+  const uint64_t head = OBX_GH_COUNTER_WORDS * 8;
+  int rc = grow(h.d_ghash, h.ghash_cap,
+                head + obx_gh_table_bytes(slots, ph.n_aggs), 1);
+  if (rc != OBX_SUCCESS) return rc;
+  unsigned long long *counters = (unsigned long long *)h.d_ghash;
+  const obx_gh_dev view = obx_gh_view(h.d_ghash + head, slots, ph.n_aggs);
+  ctx->last_group_slots = slots;
+  const uint64_t words = slots * (2 + 4 * (uint64_t)ph.n_aggs);
+  uint64_t g = (words + OBX_WG_HOST - 1) / OBX_WG_HOST;
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(k_group_hash_init, dim3((uint32_t)g), dim3(OBX_WG_HOST),
+                     0, ctx->stream, view, counters, min_mask, max_mask);
+  HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+  launch(view, ctx->max_groups, counters);
+  HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+  unsigned long long cnt[OBX_GH_COUNTER_WORDS];
+  HIP_TRY(hipMemcpyAsync(ctx->h_result, counters, sizeof(cnt),
+                         hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  memcpy(cnt, ctx->h_result, sizeof(cnt));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+  ctx->last_group_ms = ms;
+  uint64_t n_live = 0;
+  for (int i = 0; i < 8; i++) n_live += cnt[OBX_GH_WINNERS + i];
+  if (obx_gh_refused(n_live, cnt[2], ctx->max_groups))
+    return OBX_BUF_NOT_ENOUGH;
+
+  const uint32_t rec_words = 2 + 4 * ph.n_aggs;
+  rc = grow(h.d_grecs, h.grecs_cap, n_live * rec_words * 8, 1);
+  if (rc != OBX_SUCCESS) return rc;
+  if (n_live) {
+    g = slots / OBX_WG_HOST;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(k_group_compact, dim3((uint32_t)g), dim3(OBX_WG_HOST),
+                       0, ctx->stream, view, counters + OBX_GH_CURSOR,
+                       (unsigned long long *)h.d_grecs, n_live);
+    h.h_grecs.resize(n_live * rec_words);
+    HIP_TRY(hipMemcpyAsync(h.h_grecs.data(), h.d_grecs,
+                           n_live * rec_words * 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  std::vector<live_group> live(n_live);
+  for (uint64_t i = 0; i < n_live; i++) {
+    const unsigned long long *rec = h.h_grecs.data() + i * rec_words;
+    live[i] = {rec[0], rec[1], rec + 2};
+  }
+  return groups_to_rows(h, live, cnt, key_len, agg, out);
+}
+
 /* bit a: cell a is a MIN / a MAX, so the empty group table starts it at its
    sentinel (k_gtable_init). kind_of(a) is the cell's kind, as in the kernels */
 struct minmax_masks { uint32_t min = 0, max = 0; };
@@ -1368,18 +1465,22 @@ static void reset_last_scan(obx_gpu_ctx *ctx) {
   ctx->last_bdesc = 0;
   ctx->last_joint = 0;
   ctx->bdesc_built = false;
+  ctx->last_group_slots = 0;
+  ctx->last_group_ms = 0.0;
 }
 
 /* the tail, after the scan kernel is queued: close the timed region with
    the copy of table + counters (one allocation, one copy into the pinned
    buffer), take the growth path when an LDS table overflowed or the global
-   table was full (counters[1]; launch_direct as rerun_direct's launch), and
-   turn the table into rows */
-template <class LAUNCH>
+   table was full (counters[1]; launch_direct as rerun_direct's launch, or,
+   under a cap above OBX_GTABLE_BIG, launch_hash as rerun_hash's: straight to
+   the sized table, two scans and not three), and turn the table into rows */
+template <class LAUNCH, class LAUNCH_HASH>
 static int finish_agg_scan(obx_gpu_ctx *ctx, obx_handle &h,
                            const dev_plan_hdr &ph, minmax_masks mm,
                            uint8_t key_len, const obx_agg_desc *agg,
-                           obx_agg_result *out, LAUNCH launch_direct) {
+                           obx_agg_result *out, LAUNCH launch_direct,
+                           LAUNCH_HASH launch_hash) {
   int rc = end_timed(ctx, true, h.d_gtable,
                      OBX_RESULT_BYTES(OBX_GTABLE_SLOTS));
   if (rc != OBX_SUCCESS) return rc;
@@ -1388,6 +1489,9 @@ static int finish_agg_scan(obx_gpu_ctx *ctx, obx_handle &h,
   unsigned long long cnt[16];
   memcpy(cnt, gt + OBX_GTABLE_SLOTS, sizeof(cnt));
   if (cnt[1] != 0) {
+    if (ctx->max_groups > OBX_GTABLE_BIG)
+      return rerun_hash(ctx, h, ph, mm.min, mm.max, key_len, agg, out,
+                        launch_hash);
     rc = rerun_direct(ctx, h, ph, mm.min, mm.max, &n_gt, cnt, launch_direct);
     if (rc != OBX_SUCCESS) return rc;
   }
@@ -1489,6 +1593,13 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
                            dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
                            h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
                            ph, big, big_counters);
+      },
+      [&](const obx_gh_dev &table, uint64_t max_groups,
+          unsigned long long *counters) {
+        hipLaunchKernelGGL(k_scan_agg_hash, dim3(grid_for(h.n_blocks)),
+                           dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
+                           h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
+                           ph, table, max_groups, counters);
       });
 }
 
@@ -1598,7 +1709,75 @@ extern "C" int obx_gpu_scan_join_agg(obx_gpu_ctx *ctx, int handle,
                            dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
                            h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
                            ph, dj, big, big_counters);
+      },
+      [&](const obx_gh_dev &table, uint64_t max_groups,
+          unsigned long long *counters) {
+        hipLaunchKernelGGL(k_scan_join_agg_hash, dim3(grid_for(h.n_blocks)),
+                           dim3(OBX_WG_HOST), 0, ctx->stream, h.d_buf,
+                           h.d_blocks, h.n_blocks, h.d_pleaves, h.d_bleaves,
+                           ph, dj, table, max_groups, counters);
       });
+}
+
+/* ---- the cap on a scan's distinct groups (obx.h) ------------------------ */
+extern "C" int obx_gpu_set_max_groups(obx_gpu_ctx *ctx, uint64_t max_groups) {
+  if (!ctx || max_groups < OBX_GTABLE_BIG) return OBX_INVALID_ARGUMENT;
+  if (max_groups > OBX_GH_MAX_GROUPS) return OBX_NOT_SUPPORTED;
+  ctx->max_groups = max_groups;
+  return OBX_SUCCESS;
+}
+
+extern "C" uint64_t obx_gpu_max_groups(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->max_groups : 0;
+}
+
+extern "C" uint64_t obx_gpu_last_group_slots(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->last_group_slots : 0;
+}
+
+extern "C" double obx_gpu_last_group_ms(obx_gpu_ctx *ctx) {
+  return ctx ? ctx->last_group_ms : -1.0;
+}
+
+/* TEST INFRASTRUCTURE: the sized table over host memory, by the sizing and
+   insert functions the kernels run. No HIP call. Keys go in one by one, in
+   order; the stop word is looked at before the first key and then after
+   every in_flight keys (before every key when in_flight is 0), as a grid
+   that inserts in_flight rows between two looks would. *found = keys of the
+   input that a lookup finds afterwards (all of them, unless the scan
+   stopped). */
+extern "C" int obx_gpu_group_hash_host_model(
+    const uint64_t *keys, uint64_t n, uint64_t max_groups, uint64_t in_flight,
+    uint32_t n_aggs, uint64_t *slots_out, uint64_t *live_out,
+    uint64_t *max_probe_out, uint64_t *found_out, uint64_t *bytes_out) {
+  if ((n && !keys) || n_aggs > OBX_DEV_MAX_AGGS ||
+      max_groups < OBX_GTABLE_BIG)
+    return OBX_INVALID_ARGUMENT;
+  if (max_groups > OBX_GH_MAX_GROUPS) return OBX_NOT_SUPPORTED;
+  const uint64_t slots = obx_gh_slots(max_groups, n, in_flight);
+  /* the model needs the keys only: counts and cells are never touched */
+  std::vector<unsigned long long> store(slots, OBX_KEY_EMPTY);
+  const obx_gh_dev v = obx_gh_view(store.data(), slots, n_aggs);
+  uint64_t live = 0, full = 0, max_probe = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if ((in_flight == 0 || i % in_flight == 0) &&
+        (live > max_groups || full))
+      break;
+    bool won = false;
+    uint64_t steps = 0;
+    if (obx_gh_find_or_insert(v, keys[i], &won, &steps) < 0) full++;
+    live += won;
+    if (steps > max_probe) max_probe = steps;
+  }
+  uint64_t found = 0;
+  for (uint64_t i = 0; i < n; i++) found += obx_gh_find(v, keys[i]) >= 0;
+  if (slots_out) *slots_out = slots;
+  if (live_out) *live_out = live;
+  if (max_probe_out) *max_probe_out = max_probe;
+  if (found_out) *found_out = found;
+  if (bytes_out) *bytes_out = obx_gh_table_bytes(slots, n_aggs);
+  return obx_gh_refused(live, full, max_groups) ? OBX_BUF_NOT_ENOUGH
+                                                : OBX_SUCCESS;
 }
 
 extern "C" uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "obx_dev.h"
+#include "obx_grouphash.h"
 #include "obx_keymap.h"
 #include "obx_keyset.h"
 #include "obx_project.h"
@@ -150,6 +151,23 @@ extern "C" __global__ void k_scan_join_agg_direct(
     const blk_leaf *, const dev_plan_hdr, const dev_join, gslot *,
     unsigned long long *);
 
+/* the sized group table (obx_grouphash.h): the growth-path body on it, its
+   init, and the compaction of its live slots into records */
+extern "C" __global__ void k_scan_agg_hash(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const obx_gh_dev, uint64_t,
+    unsigned long long *);
+extern "C" __global__ void k_scan_join_agg_hash(
+    const uint8_t *, const dev_block *, uint32_t, const dev_leaf *,
+    const blk_leaf *, const dev_plan_hdr, const dev_join, const obx_gh_dev,
+    uint64_t, unsigned long long *);
+extern "C" __global__ void k_group_hash_init(const obx_gh_dev,
+                                             unsigned long long *, uint32_t,
+                                             uint32_t);
+extern "C" __global__ void k_group_compact(const obx_gh_dev,
+                                           unsigned long long *,
+                                           unsigned long long *, uint64_t);
+
 #define HIP_TRY(x)                                        \
   do {                                                    \
     hipError_t _e = (x);                                  \
@@ -199,6 +217,17 @@ struct obx_handle {
   uint8_t *d_decode_out[OBX_DEV_MAX_COLS] = {};
   uint64_t last_survivors = 0;
   gslot *d_gtable_big = nullptr; /* high-cardinality direct kernel table */
+  /* the sized group table of a scan past OBX_GTABLE_BIG groups: its counter
+     block (OBX_GH_COUNTER_WORDS) then the table, in one allocation that
+     grows only when a scan needs more; the compacted records next to it,
+     and where they land on the host. Pageable, not pinned: the copy is
+     followed at once by a sort of the same records that costs more, and a
+     grant of 2^24 groups would otherwise pin gigabytes. */
+  uint8_t *d_ghash = nullptr;
+  uint64_t ghash_cap = 0; /* bytes */
+  uint8_t *d_grecs = nullptr;
+  uint64_t grecs_cap = 0; /* bytes */
+  std::vector<unsigned long long> h_grecs;
   void *d_proj_scratch = nullptr; /* k_decode_multi proj/len/out arrays */
   /* result of the last obx_gpu_scan_project: dense vectors per projected
      position, one byte of null flags per row (bit p = position p), row
@@ -333,6 +362,10 @@ struct obx_gpu_ctx {
   /* device times of the last scan_project: filter, block offsets, gather */
   double last_proj_ms[3] = {0.0, 0.0, 0.0};
   uint32_t last_grid = 0;     /* workgroups that kernel was launched with */
+  /* most distinct groups a scan may produce (obx_gpu_set_max_groups) */
+  uint64_t max_groups = OBX_GTABLE_BIG;
+  uint64_t last_group_slots = 0; /* sized table of the last scan, 0 = none */
+  double last_group_ms = 0.0;    /* device time of that table's scan kernel */
   uint32_t n_cus = 256;
   /* pinned landing buffer for the group table + counters of a scan (sized
      for the growth-path table) */

@@ -187,7 +187,7 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_join_agg_prog_lds(
  * puts between scan_direct_body's filter and its table: a row takes part
  * when its probe key (col_value2, every encoding) is a map key, the payload
  * is spliced into the group key, and the cells of own_mask accumulate the
- * payload. */
+ * payload (through the sink the body hands in). */
 struct direct_join {
   const dev_join &dj;
   __device__ __forceinline__ bool admit(const blk_view &bv,
@@ -202,11 +202,12 @@ struct direct_join {
   __device__ __forceinline__ uint64_t key(uint64_t rk, uint64_t pv) const {
     return obx_join_key(dj, rk, pv);
   }
+  template <class SINK>
   __device__ __forceinline__ bool own(uint32_t a, uint64_t pv,
-                                      unsigned long long *cell) const {
+                                      const SINK sink) const {
     if (!((dj.own_mask >> a) & 1)) return false;
     agg_term(dj.kind[a], false, 0, 0, (int64_t)pv, false, 0, false, 0, false,
-             gcell_sink{cell});
+             sink);
     return true;
   }
 };
@@ -217,6 +218,17 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_join_agg_direct(
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
     const dev_join dj, gslot *__restrict__ gtable,
     unsigned long long *__restrict__ counters) {
-  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph, gtable,
-                   counters, direct_join{dj});
+  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
+                   gslot_table{gtable}, counters, direct_join{dj});
+}
+
+/* the same on the sized table (k_scan_agg_hash, obx_kernels.hip) */
+extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_join_agg_hash(
+    const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
+    uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
+    const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
+    const dev_join dj, const obx_gh_dev table, uint64_t max_groups,
+    unsigned long long *__restrict__ counters) {
+  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
+                   sized_table{table, max_groups}, counters, direct_join{dj});
 }

@@ -929,6 +929,95 @@ extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_direct(
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
     gslot *__restrict__ gtable, unsigned long long *__restrict__ counters) {
-  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph, gtable,
-                   counters, no_join{});
+  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
+                   gslot_table{gtable}, counters, no_join{});
+}
+
+/* ---------------- the sized group table (obx_grouphash.h) ----------------
+ * Past OBX_GTABLE_BIG groups, under a cap the caller granted
+ * (obx_gpu_set_max_groups): the same body on a hash table in device memory
+ * sized from the cap. It counts its CAS winners and starts no further block
+ * once they pass max_groups, so a grant that is too small costs a bounded
+ * number of short probe sequences, never a table filled to the brim. The
+ * host refuses the scan iff winners > max_groups or counters[2] != 0. */
+extern "C" __global__ __launch_bounds__(WG, 2) void k_scan_agg_hash(
+    const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
+    uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
+    const blk_leaf *__restrict__ bleaves, const dev_plan_hdr ph,
+    const obx_gh_dev table, uint64_t max_groups,
+    unsigned long long *__restrict__ counters) {
+  scan_direct_body(buf, blocks, n_blocks, plan_leaves, bleaves, ph,
+                   sized_table{table, max_groups}, counters, no_join{});
+}
+
+/* Empty sized table and its zeroed counter block: one u64 word per thread
+ * and step over the three arrays (EMPTY keys, zero counts, cells at zero
+ * with limb 0 of a MIN / MAX cell at its sentinel, bit a of the masks as in
+ * k_gtable_init). 64-bit word indices: the cell array alone passes 2^32
+ * bytes long before the largest cap. */
+extern "C" __global__ void k_group_hash_init(
+    const obx_gh_dev table, unsigned long long *__restrict__ counters,
+    uint32_t min_mask, uint32_t max_mask) {
+  const uint64_t slots = obx_gh_n_slots(table);
+  const uint64_t cell_words = slots * table.n_aggs * 4;
+  const uint64_t total = 2 * slots + cell_words;
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t0 < OBX_GH_COUNTER_WORDS) counters[t0] = 0;
+  unsigned long long *keys = obx_gh_keys(table);
+  unsigned long long *counts = obx_gh_count(table, 0);
+  unsigned long long *cells = obx_gh_cell(table, 0, 0);
+  for (uint64_t i = t0; i < total; i += step) {
+    if (i < slots) {
+      keys[i] = OBX_KEY_EMPTY;
+    } else if (i < 2 * slots) {
+      counts[i - slots] = 0;
+    } else {
+      const uint64_t w = i - 2 * slots;
+      unsigned long long v = 0;
+      if ((w & 3) == 0) {
+        const uint32_t a = (uint32_t)((w >> 2) % table.n_aggs);
+        if ((min_mask >> a) & 1) v = (unsigned long long)INT64_MAX;
+        else if ((max_mask >> a) & 1) v = (unsigned long long)INT64_MIN;
+      }
+      cells[w] = v;
+    }
+  }
+}
+
+/* Live slots of a sized table -> dense records of 16 + 32 * n_aggs bytes
+ * {key, count, cells}, so the host copies n_live records and not `slots`.
+ * Every wave takes 64 slots at a time (slots is a multiple of 64): a ballot
+ * of the live lanes, one add of its popcount into the cursor by lane 0 for
+ * the wave's base, each live lane at base + its prefix. Record order is
+ * whatever the adds make it; the host sorts. out holds `cap` records: the
+ * host sized it from the winner count, and the test keeps a wrong count
+ * from writing past it. */
+extern "C" __global__ void k_group_compact(
+    const obx_gh_dev table, unsigned long long *__restrict__ cursor,
+    unsigned long long *__restrict__ out, uint64_t cap) {
+  const uint64_t slots = obx_gh_n_slots(table);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t rec_words = 2 + 4 * table.n_aggs;
+  const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const unsigned long long *keys = obx_gh_keys(table);
+  for (uint64_t s0 = wave * 64; s0 < slots; s0 += n_waves * 64) {
+    const uint64_t s = s0 + lane;
+    const unsigned long long key = keys[s];
+    const bool live = key != OBX_KEY_EMPTY;
+    const uint64_t m = __ballot(live);
+    if (!m) continue;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(cursor, (unsigned long long)__popcll(m));
+    base = (unsigned long long)__shfl((long long)base, 0, 64);
+    if (!live) continue;
+    const uint64_t at = base + __popcll(m & ((1ull << lane) - 1));
+    if (at >= cap) continue;
+    unsigned long long *rec = out + at * rec_words;
+    rec[0] = key;
+    rec[1] = *obx_gh_count(table, s);
+    const unsigned long long *c = obx_gh_cell(table, s, 0);
+    for (uint32_t w = 0; w < 4 * table.n_aggs; w++) rec[2 + w] = c[w];
+  }
 }

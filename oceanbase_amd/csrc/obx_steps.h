@@ -11,6 +11,7 @@
 #ifndef OBX_STEPS_H
 #define OBX_STEPS_H
 #include "obx_blk.h"
+#include "obx_grouphash.h"
 
 struct prog_spec { uint8_t n; uint8_t t[15]; };
 
@@ -485,15 +486,17 @@ __device__ __forceinline__ void lds_table_flush(
 }
 
 /* ---- the growth path: one body for k_scan_agg_direct and
-   k_scan_join_agg_direct. No LDS table: every surviving row resolves its key
-   in the OBX_GTABLE_BIG table (a full table is surfaced as counters[2]) and
-   accumulates with global atomics, each aggregate on its own (no
+   k_scan_join_agg_direct (the OBX_GTABLE_BIG table) and for k_scan_agg_hash
+   and k_scan_join_agg_hash (the sized table). No LDS table: every surviving
+   row resolves its key in the global table (a full table is surfaced as
+   counters[2]) and accumulates with global atomics, each aggregate on its own (no
    PROD2+PROD3 fusing); the survivor count goes to the striped counters
    8..15. AND-combined leaves only. `join` is what a join adds between the
    filter and the table:
      admit(bv, cur, ph, r, pv)  does row r take part (probe hit)? sets pv
      key(rk, pv)                the group key from the real columns' key rk
-     own(a, pv, cell)           true when cell a is the join's, accumulated
+     own(a, pv, sink)           true when cell a is the join's: its term
+                                goes to sink
    no_join is the plain scan's: every row, the key as built, no cell. ---- */
 struct no_join {
   __device__ __forceinline__ bool admit(const blk_view &, const dev_block &,
@@ -502,23 +505,181 @@ struct no_join {
   __device__ __forceinline__ uint64_t key(uint64_t rk, uint64_t) const {
     return rk;
   }
-  __device__ __forceinline__ bool own(uint32_t, uint64_t,
-                                      unsigned long long *) const {
+  template <class SINK>
+  __device__ __forceinline__ bool own(uint32_t, uint64_t, const SINK) const {
     return false;
   }
 };
 
-template <class JOIN>
+/* `table` is where the groups live, the second small policy:
+     COUNTED                    the table counts its CAS winners and the scan
+                                stops once they pass the grant
+     find(key, won)             find-or-insert: the slot, or < 0 when full
+     count(slot)                the slot's row count word
+     cell(slot, a)              aggregate a's 256-bit cell (gcell_sink)
+     stop(counters, lane)       wave-uniform: start no further block
+     won(counters, w, ...)      take this iteration's winners into the count
+     FOLD                       adjacent lanes with one key fold their rows
+                                into the first of them before the table is
+                                touched (wave_run, below)
+   gslot_table is the OBX_GTABLE_BIG table of gslots: full means every slot
+   holds another key, nothing is counted, nothing stops the scan. */
+struct gslot_table {
+  static constexpr bool COUNTED = false;
+  static constexpr bool FOLD = false;
+  gslot *gt;
+  __device__ __forceinline__ int64_t find(uint64_t key, bool &) const {
+    return gtable_slot<OBX_GTABLE_BIG_SHIFT>(gt, key);
+  }
+  __device__ __forceinline__ unsigned long long *count(int64_t s) const {
+    return &gt[s].count;
+  }
+  __device__ __forceinline__ unsigned long long *cell(int64_t s,
+                                                      uint32_t a) const {
+    return gt[s].cells[a];
+  }
+  __device__ __forceinline__ bool stop(const unsigned long long *,
+                                       uint32_t) const { return false; }
+  __device__ __forceinline__ void won(unsigned long long *, bool, uint32_t,
+                                      uint32_t) const {}
+};
+
+/* the sized table (obx_grouphash.h) behind a grant of max_groups. Winners
+   are counted per wave: a ballot over the lanes still in this iteration, one
+   add of its popcount by the first winner lane into one of 8 striped words,
+   and only when the iteration had a winner. stop() reads those 8 words (one
+   64-byte line) and counters[2] at agent scope. */
+struct sized_table {
+  static constexpr bool COUNTED = true;
+  /* measured, profiles/r11_group_hash.md: 13-42 % off the kernel on keys
+     clustered in runs of 4, nothing beyond spread on random keys */
+  static constexpr bool FOLD = true;
+  obx_gh_dev v;
+  uint64_t max_groups;
+  __device__ __forceinline__ int64_t find(uint64_t key, bool &w) const {
+    uint64_t steps;
+    return obx_gh_find_or_insert(v, key, &w, &steps);
+  }
+  __device__ __forceinline__ unsigned long long *count(int64_t s) const {
+    return obx_gh_count(v, (uint64_t)s);
+  }
+  __device__ __forceinline__ unsigned long long *cell(int64_t s,
+                                                      uint32_t a) const {
+    return obx_gh_cell(v, (uint64_t)s, a);
+  }
+  __device__ __forceinline__ bool stop(unsigned long long *counters,
+                                       uint32_t lane) const {
+    unsigned long long w = 0;
+    if (lane < 8)
+      w = __hip_atomic_load(&counters[OBX_GH_WINNERS + lane],
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (lane == 8)
+      w = __hip_atomic_load(&counters[2], __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT)
+              ? max_groups + 1 : 0;
+    for (int off = 8; off > 0; off >>= 1)
+      w += (unsigned long long)__shfl_xor((long long)w, off, 64);
+    /* lanes 0..15 now hold the sum of lanes 0..15 */
+    w = (unsigned long long)__shfl((long long)w, 0, 64);
+    return w > max_groups;
+  }
+  __device__ __forceinline__ void won(unsigned long long *counters, bool w,
+                                      uint32_t lane, uint32_t wave_id) const {
+    const uint64_t m = __ballot(w);
+    if (w && lane == (uint32_t)__ffsll((unsigned long long)m) - 1)
+      atomicAdd(&counters[OBX_GH_WINNERS + (wave_id & 7)],
+                (unsigned long long)__popcll(m));
+  }
+};
+
+/* ---- the wave fold: rows of one key in adjacent lanes (a table clustered
+   on the group column, l_orderkey's shape) reach the table as one row. A
+   run is a maximal stretch of lanes with equal keys; a lane without a row
+   carries OBX_KEY_EMPTY and so never joins a row's run. Its first lane
+   leads: it alone finds the slot, adds the run's length to the count and
+   applies every aggregate's folded term. All 64 lanes call these. ---- */
+struct wave_run {
+  bool lead;     /* first lane of a run of rows */
+  uint32_t end;  /* one past the run's last lane */
+  uint32_t n;    /* lanes in the run, from this one on */
+};
+
+__device__ __forceinline__ wave_run wave_run_of(uint64_t key, bool live,
+                                                uint32_t lane) {
+  const uint64_t prev = (uint64_t)__shfl_up((long long)key, 1, 64);
+  const bool head = lane == 0 || prev != key;
+  const uint64_t heads = __ballot(head);
+  const uint64_t above = lane == 63 ? 0 : heads >> (lane + 1);
+  wave_run w;
+  w.end = above ? lane + 1 + (uint32_t)__ffsll((unsigned long long)above) - 1
+                : 64;
+  w.n = w.end - lane;
+  w.lead = head && live;
+  return w;
+}
+
+/* one row's term, held back: what agg_term would have done to a cell */
+struct held_term {
+  uint64_t lo, hi;
+  uint32_t op; /* 0 nothing, 1 add {lo, hi}, 2 MIN of lo, 3 MAX of lo */
+};
+struct hold_sink {
+  held_term *t;
+  __device__ __forceinline__ void count() const {
+    t->op = 1; t->lo = 1; t->hi = 0;
+  }
+  __device__ __forceinline__ void add(i128v v) const {
+    t->op = 1; t->lo = v.lo; t->hi = v.hi;
+  }
+  __device__ __forceinline__ void add_mate(i128v) const {}
+  __device__ __forceinline__ void minmax(int64_t v, bool is_min) const {
+    t->op = is_min ? 2 : 3; t->lo = (uint64_t)v; t->hi = 0;
+  }
+};
+
+/* fold the run's held terms into its first lane (segmented reduction: a
+   lane takes the term `off` lanes up while that lane is inside its run) */
+__device__ __forceinline__ void wave_run_fold(held_term &t, const wave_run &w,
+                                              uint32_t lane) {
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint64_t olo = (uint64_t)__shfl_down((long long)t.lo, off, 64);
+    const uint64_t ohi = (uint64_t)__shfl_down((long long)t.hi, off, 64);
+    const uint32_t oop = (uint32_t)__shfl_down((int)t.op, off, 64);
+    if (lane + off >= w.end || !oop) continue;
+    if (!t.op) {
+      t.lo = olo; t.hi = ohi; t.op = oop;
+    } else if (oop == 1) {
+      const uint64_t nlo = t.lo + olo;
+      t.hi += ohi + (nlo < olo);
+      t.lo = nlo;
+    } else if (oop == 2 ? (int64_t)olo < (int64_t)t.lo
+                        : (int64_t)olo > (int64_t)t.lo) {
+      t.lo = olo;
+    }
+  }
+}
+
+template <class SINK>
+__device__ __forceinline__ void held_apply(const held_term &t,
+                                           const SINK sink) {
+  i128v v; v.lo = t.lo; v.hi = t.hi;
+  if (t.op == 1) sink.add(v);
+  else if (t.op) sink.minmax((int64_t)t.lo, t.op == 2);
+}
+
+template <class JOIN, class TABLE>
 __device__ __forceinline__ void scan_direct_body(
     const uint8_t *__restrict__ buf, const dev_block *__restrict__ blocks,
     uint32_t n_blocks, const dev_leaf *__restrict__ plan_leaves,
     const blk_leaf *__restrict__ bleaves, const dev_plan_hdr &ph,
-    gslot *__restrict__ gtable, unsigned long long *__restrict__ counters,
+    const TABLE table, unsigned long long *__restrict__ counters,
     const JOIN join) {
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63, wv = tid >> 6;
   unsigned long long lane_cnt = 0;
   for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    if constexpr (TABLE::COUNTED)
+      if (table.stop(counters, lane)) break;
     const dev_block &cur = blocks[b];
     const blk_leaf *bl = bleaves + (size_t)b * ph.n_leaves;
     bool skip = false;
@@ -531,36 +692,63 @@ __device__ __forceinline__ void scan_direct_body(
     if (ph.n_group_cols > 1) gd1 = &cur.cols[ph.need_cols[ph.group_idx[1]]];
     const uint32_t kl0 = ph.group_len[0], kl1 = ph.group_len[1];
     const uint32_t rows = cur.row_count;
-    for (uint32_t r = tid; r < rows; r += WG) {
-      bool live = true;
+    /* a folding table keeps the wave together to the end of the window:
+       rows past the block and rows the filter or the join drops ride along
+       as lanes without a row. Otherwise such a lane leaves at once. */
+    const uint32_t span = TABLE::FOLD ? (rows + WG - 1) / WG * WG : rows;
+    for (uint32_t r = tid; r < span; r += WG) {
+      bool live = !TABLE::FOLD || r < rows;
       for (uint32_t i = 0; live && i < ph.n_leaves; i++)
         live = leaf_match(bv, cur, plan_leaves[i], bl[i], r);
-      if (!live) continue;
+      if constexpr (!TABLE::FOLD) { if (!live) continue; }
       uint64_t pv = 0;
-      if (!join.admit(bv, cur, ph, r, pv)) continue;
-      lane_cnt++;
-      const uint64_t key = join.key(
-          build_group_key(bv, ph.n_group_cols, gd0, gd1, kl0, kl1, r), pv);
-      int gi = gtable_slot<OBX_GTABLE_BIG_SHIFT>(gtable, key);
-      if (gi < 0) { /* global table full: surfaced as counters[2] */
-        atomicAdd(&counters[2], 1ull);
-        continue;
+      if (live && !join.admit(bv, cur, ph, r, pv)) live = false;
+      if constexpr (!TABLE::FOLD) { if (!live) continue; }
+      uint64_t key = OBX_KEY_EMPTY;
+      if (live) {
+        lane_cnt++;
+        key = join.key(
+            build_group_key(bv, ph.n_group_cols, gd0, gd1, kl0, kl1, r), pv);
       }
-      atomicAdd(&gtable[gi].count, 1ull);
+      wave_run run = {live, lane + 1, 1};
+      if constexpr (TABLE::FOLD) run = wave_run_of(key, live, lane);
+      int64_t gi = -1;
+      if (run.lead) {
+        bool won = false;
+        gi = table.find(key, won);
+        if constexpr (TABLE::COUNTED)
+          table.won(counters, won, lane, blockIdx.x * WAVES + wv);
+        if (gi < 0) /* global table full: surfaced as counters[2] */
+          atomicAdd(&counters[2], (unsigned long long)run.n);
+        else
+          atomicAdd(table.count(gi), (unsigned long long)run.n);
+      }
+      if constexpr (!TABLE::FOLD) { if (gi < 0) continue; }
       for (uint32_t a = 0; a < ph.n_aggs; a++) {
-        if (join.own(a, pv, gtable[gi].cells[a])) continue;
-        const dev_agg ag = ph.aggs[a];
-        if (ag.kind == 0 && ag.ia == 0xFF) continue; /* COUNT(*): count */
-        bool na = false, nb = false, nc = false;
-        int64_t va = 0, vb = 0, vc = 0;
-        if (ag.ia != 0xFF)
-          va = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ia]], r, na);
-        if (ag.kind >= 4 && ag.ib != 0xFF)
-          vb = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ib]], r, nb);
-        if (ag.kind == 5 && ag.ic != 0xFF)
-          vc = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ic]], r, nc);
-        agg_term(ag.kind, false, ag.one_b, ag.one_c, va, na, vb, nb, vc, nc,
-                 gcell_sink{gtable[gi].cells[a]});
+        /* row r's term of aggregate a, into whatever sink takes it */
+        auto term_into = [&](auto sink) {
+          if (join.own(a, pv, sink)) return;
+          const dev_agg ag = ph.aggs[a];
+          if (ag.kind == 0 && ag.ia == 0xFF) return; /* COUNT(*): count */
+          bool na = false, nb = false, nc = false;
+          int64_t va = 0, vb = 0, vc = 0;
+          if (ag.ia != 0xFF)
+            va = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ia]], r, na);
+          if (ag.kind >= 4 && ag.ib != 0xFF)
+            vb = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ib]], r, nb);
+          if (ag.kind == 5 && ag.ic != 0xFF)
+            vc = col_value2(bv, cur, cur.cols[ph.need_cols[ag.ic]], r, nc);
+          agg_term(ag.kind, false, ag.one_b, ag.one_c, va, na, vb, nb, vc, nc,
+                   sink);
+        };
+        if constexpr (TABLE::FOLD) {
+          held_term t = {0, 0, 0};
+          if (live) term_into(hold_sink{&t});
+          wave_run_fold(t, run, lane);
+          if (run.lead && gi >= 0) held_apply(t, gcell_sink{table.cell(gi, a)});
+        } else {
+          term_into(gcell_sink{table.cell(gi, a)});
+        }
       }
     }
   }

@@ -126,6 +126,19 @@ def _load():
                                           C.POINTER(abi.JoinDesc),
                                           C.POINTER(abi.AggDesc),
                                           C.POINTER(abi.AggResult)]
+    lib.obx_gpu_set_max_groups.restype = C.c_int
+    lib.obx_gpu_set_max_groups.argtypes = [C.c_void_p, C.c_uint64]
+    lib.obx_gpu_max_groups.restype = C.c_uint64
+    lib.obx_gpu_max_groups.argtypes = [C.c_void_p]
+    lib.obx_gpu_last_group_slots.restype = C.c_uint64
+    lib.obx_gpu_last_group_slots.argtypes = [C.c_void_p]
+    lib.obx_gpu_last_group_ms.restype = C.c_double
+    lib.obx_gpu_last_group_ms.argtypes = [C.c_void_p]
+    lib.obx_gpu_group_hash_host_model.restype = C.c_int
+    lib.obx_gpu_group_hash_host_model.argtypes = [
+        C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     for f in ("obx_gpu_total_rows", "obx_gpu_total_bytes",
               "obx_gpu_last_survivors"):
         getattr(lib, f).restype = C.c_uint64
@@ -220,6 +233,35 @@ def keymap_host_model(keys, payloads, spec, probe=(), kind=0):
     if rc != 0:
         raise KeymapError("obx_gpu_keymap_host_model", rc)
     return hit.astype(bool), pay, info
+
+
+class GroupCapError(RuntimeError):
+    """obx_gpu_set_max_groups refused the cap; .rc is the engine's status."""
+
+    def __init__(self, what, rc):
+        super().__init__(f"{what} failed: {rc}")
+        self.rc = rc
+
+
+def group_hash_host_model(keys, max_groups, in_flight=0, n_aggs=2):
+    """TEST INFRASTRUCTURE: run the sized group table in host memory with
+    the inline sizing and find-or-insert functions the device runs: uint64
+    keys inserted in order, the stop word looked at every in_flight keys.
+    Needs no GPU. Returns a dict: rc (0 or OBX_BUF_NOT_ENOUGH), slots, live
+    (keys in the table), max_probe (longest probe sequence, in slots looked
+    at), found (input keys a lookup finds afterwards), bytes (of the table at
+    n_aggs aggregates). Raises GroupCapError for a cap out of range."""
+    import numpy as np
+    k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
+    out = [C.c_uint64(0) for _ in range(5)]
+    rc = lib().obx_gpu_group_hash_host_model(
+        k.ctypes.data_as(C.c_void_p), k.size, max_groups, in_flight, n_aggs,
+        *[C.byref(o) for o in out])
+    if rc not in (0, abi.OBX_BUF_NOT_ENOUGH):
+        raise GroupCapError("obx_gpu_group_hash_host_model", rc)
+    return dict(rc=rc, slots=out[0].value, live=out[1].value,
+                max_probe=out[2].value, found=out[3].value,
+                bytes=out[4].value)
 
 
 class GpuEngine:
@@ -533,6 +575,27 @@ class GpuEngine:
             if start >= total.value or n_out.value == 0:
                 break
         return rows
+
+    # ---- the cap on a scan's distinct groups ------------------------------
+    def set_max_groups(self, max_groups):
+        """Grant scans of this engine up to max_groups distinct groups
+        (default and minimum abi.GROUP_CAP_DEFAULT, at most
+        abi.GROUP_CAP_MAX). Raises GroupCapError (with .rc) otherwise."""
+        rc = self._lib.obx_gpu_set_max_groups(self._ctx, max_groups)
+        if rc != 0:
+            raise GroupCapError("obx_gpu_set_max_groups", rc)
+
+    def max_groups(self):
+        return int(self._lib.obx_gpu_max_groups(self._ctx))
+
+    def last_group_slots(self):
+        """Slots of the sized group table the last aggregate scan ran on;
+        0 when it did not need one."""
+        return int(self._lib.obx_gpu_last_group_slots(self._ctx))
+
+    def last_group_ms(self):
+        """Device ms of the last scan's sized-table kernel (0 = none ran)."""
+        return float(self._lib.obx_gpu_last_group_ms(self._ctx))
 
     def last_kernel_ms(self):
         return float(self._lib.obx_gpu_last_kernel_ms(self._ctx))
