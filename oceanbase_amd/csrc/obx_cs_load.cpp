@@ -337,7 +337,7 @@ static int parse_cs_block(const uint8_t *buf, size_t len, uint64_t src_base,
 
 /* host half: parse every block, plan the arena (h.total_bytes) and the
    decode tasks, and fold each chunk's descriptor into h's facts */
-int obx_cs_host_load(const obx_blockset *bs, obx_handle &h,
+int obx_cs_host_load(const obx_blockset *bs, obx_table_facts &h,
                      std::vector<dev_block> &blocks, obx_cs_plan *plan) {
   if (!bs->data || !bs->cols) return OBX_INVALID_ARGUMENT;
   obx_cs_plan facts_only;

@@ -65,8 +65,8 @@ extern "C" int obx_gpu_close(obx_gpu_ctx *ctx) {
 }
 
 /* the one place a handle's device memory is released (d_counters is the
-   tail of d_gtable). Never-loaded handles, as the GPU-free probes build
-   them, hold only nulls and make no HIP call. */
+   tail of d_gtable). A handle whose load failed early holds only nulls and
+   makes no HIP call. */
 obx_handle::~obx_handle() {
   void *owned[] = {d_buf, d_blocks, d_bleaves, d_pleaves, d_gtable,
                    d_gtable_big, d_ghash, d_grecs, d_proj_scratch, d_bitmap, d_row_ids,
@@ -89,57 +89,6 @@ obx_handle *obx_handle_lookup(obx_gpu_ctx *ctx, int handle) {
   return ctx->handles[handle].get();
 }
 
-/* Load-time payload checksum (the reference verifies data_checksum_ when a
- * block enters the block cache, before any decode — check_payload_checksum,
- * ob_micro_block_header.cpp:257-271). ob_crc64_sse42 semantics = CRC-32C in
- * a u64 accumulator; the host has the crc32 instruction, same as the
- * reference's hardware path. Independent of the oracle's implementation. */
-__attribute__((target("sse4.2")))
-static uint64_t host_crc32c(const uint8_t *buf, int64_t len) {
-  uint64_t crc = 0;
-  int64_t i = 0;
-  for (; i + 8 <= len; i += 8) {
-    uint64_t w;
-    memcpy(&w, buf + i, 8);
-    crc = __builtin_ia32_crc32di(crc, w);
-  }
-  for (; i < len; i++) crc = __builtin_ia32_crc32qi((uint32_t)crc, buf[i]);
-  return crc;
-}
-
-/* grid of the persistent scan JIT (obx_jit_scan.inc): OBX_JIT_GRID_WAVES
-   times what is resident at wpb workgroups per CU, and never more
-   workgroups than blocks. Each workgroup flushes once, a handful of global
-   atomics per live cell, so the grid is free to be finer than the resident
-   set: the dispatcher then evens out CU-to-CU differences and the tail
-   shrinks to one short workgroup. Measured on Q1 SF=100 (profiles/
-   r03_q1_flush.md): 1x 3.00 ms, 2x 2.90, 4x 2.80, 8x 2.76, 12x 2.78,
-   16x 2.82, 32x 3.70; 1.5x (a half-empty second wave) 3.22. The one
-   source of that grid: the strategy proves its i64 accumulator bound for
-   it and the launch uses it. OBX_JIT_SGRID=n caps it at n workgroups (the
-   scan-side sibling of OBX_JIT_FGRID): small tables then give a workgroup
-   several blocks, which the block loop's tests and A/B runs need. */
-#define OBX_JIT_GRID_WAVES 8
-static uint32_t jit_grid_for(uint32_t n_blocks, uint32_t n_cus, int wpb) {
-  uint64_t g = (uint64_t)(n_cus ? n_cus : 1) * (uint32_t)(wpb > 0 ? wpb : 1) *
-               OBX_JIT_GRID_WAVES;
-  if (const char *sg = getenv("OBX_JIT_SGRID")) {
-    const long v = atol(sg);
-    if (v >= 1 && (uint64_t)v < g) g = (uint64_t)v;
-  }
-  if (g > n_blocks) g = n_blocks;
-  return g ? (uint32_t)g : 1;
-}
-
-/* Rows one workgroup of that grid can sweep: its share of the blocks times
-   the rows of the largest block. The bound behind the i64 windows and the
-   row count packed into the joint cells. */
-static uint64_t jit_wg_rows(const obx_handle &h, uint32_t grid) {
-  if (!grid) grid = 1;
-  return (uint64_t)((h.n_blocks + grid - 1) / grid) *
-         (h.max_block_rows ? h.max_block_rows : 4096);
-}
-
 /* device-side fill of an empty group table (EMPTY keys, zero cells, MIN/MAX
    sentinels by aggregate mask) and of the tail_words counters behind it */
 static void gtable_init(gslot *gt, uint32_t n_slots, uint32_t tail_words,
@@ -150,346 +99,6 @@ static void gtable_init(gslot *gt, uint32_t n_slots, uint32_t tail_words,
   hipLaunchKernelGGL(k_gtable_init, dim3((words + OBX_WG_HOST - 1) / OBX_WG_HOST),
                      dim3(OBX_WG_HOST), 0, stream, (unsigned long long *)gt,
                      n_slots, tail_words, min_mask, max_mask);
-}
-
-/* fold the newest block's row of col_class / col_cnt into the per-column
-   facts build_plan and jit_blocks_ok test. obx_fold_block appends that row
-   from a parsed block; the GPU-free probes append synthetic ones. */
-static void summarize_col_classes(obx_handle &h) {
-  const uint32_t nc = h.n_cols;
-  const bool first = h.col_class.size() == nc;
-  const uint8_t *cls = h.col_class.data() + h.col_class.size() - nc;
-  const uint8_t *cnt = h.col_cnt.data() + h.col_cnt.size() - nc;
-  for (uint32_t c = 0; c < nc; c++) {
-    const uint8_t k = cls[c];
-    if (first) h.col_grp16_every[c] = true;
-    if ((k & 0xF) == 5) h.col_span_any[c] = true;
-    if ((k & 0xF) != 1 || cnt[c] >= 16) h.col_grp16_every[c] = false;
-    if ((k & 0xF) > 3 || (k & 0x10)) h.col_slow_any[c] = true;
-    if (cnt[c] > h.col_cnt_max[c]) h.col_cnt_max[c] = cnt[c];
-  }
-}
-
-void obx_fold_block(obx_handle &h, const dev_block &db) {
-  const bool first = h.col_class.empty();
-  if ((db.block_byte & 15) ||
-      (uint64_t)db.block_len + 24 > OBX_LDS_STAGE_BYTES ||
-      db.row_count > 4096 /* OBX_MAX_BLOCK_ROWS */)
-    h.lds_ok = false;
-  for (uint16_t c = 0; c < h.n_cols; c++) {
-    const dev_col &dc = db.cols[c];
-    uint8_t cls;
-    switch (dc.enc) {
-      case OBX_D_RAW: cls = 0; break;
-      case OBX_D_DICT: cls = 1; break;
-      case OBX_D_INTDIFF: cls = 2; break;
-      case OBX_D_CONST: cls = dc.runs == 0 ? 3 : 4; break;
-      case OBX_D_EQUAL: case OBX_D_SUBSTR:
-        cls = 5; break; /* span: no device group keys */
-      default: cls = 4; break;
-    }
-    if (dc.flags & OBX_DF_STRING) cls |= 0x10;
-    h.col_class.push_back(cls);
-    h.col_cnt.push_back((uint8_t)(dc.count > 254 ? 255 : dc.count));
-    if (first) {
-      h.col_dict_every[c] = true;
-      h.col_dict_any[c] = true;
-      h.col_raw8_every[c] = true;
-      h.col_rangefam_every[c] = true;
-    }
-    if ((cls & 0xF) != 1 || (cls & 0x10) || dc.count > 63)
-      h.col_dict_every[c] = false;
-    if ((cls & 0xF) != 1 || dc.count > 63)
-      h.col_dict_any[c] = false; /* dict (possibly char) everywhere */
-    if (!(dc.enc == OBX_D_RAW && !(dc.flags & OBX_DF_BITPACK) &&
-          !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT) &&
-          dc.width == 8 && (dc.data_bit & 63) == 0))
-      h.col_raw8_every[c] = false;
-    if (!((dc.enc == OBX_D_RAW || dc.enc == OBX_D_INTDIFF) &&
-          !(dc.flags & OBX_DF_STRING) && !(dc.flags & OBX_DF_HAS_EXT)))
-      h.col_rangefam_every[c] = false;
-    if (dc.count > h.col_maxcnt[c]) h.col_maxcnt[c] = dc.count;
-    if (dc.flags & OBX_DF_HAS_EXT) h.col_ext_any[c] = true;
-    uint32_t w = 255; /* no packed stream: blocks multi-row reads */
-    if (dc.enc == OBX_D_RAW || dc.enc == OBX_D_DICT || dc.enc == OBX_D_INTDIFF)
-      w = (dc.flags & OBX_DF_BITPACK) ? dc.width : (uint32_t)dc.width * 8;
-    if (w > h.col_maxw[c]) h.col_maxw[c] = w;
-    uint64_t slot;
-    if (!obx_bdesc_pack_col(&dc, db.block_byte, &slot))
-      h.col_bdesc_unfit[c] = true;
-  }
-  summarize_col_classes(h);
-  if (db.row_count > h.max_block_rows) h.max_block_rows = db.row_count;
-  if (db.block_len > h.max_block_len) h.max_block_len = db.block_len;
-  h.n_blocks++;
-  h.total_rows += db.row_count;
-}
-
-/* ---- host block parsing (mirrors ObMicroBlockDecoder pointer math,
- * ob_micro_block_decoder.cpp:360-380, and the per-decoder init functions
- * cited in oracle/obx_codec.c) ------------------------------------------- */
-static int parse_block(const obx_col_schema *cols, uint16_t n_cols,
-                       const uint8_t *block, uint64_t dev_off,
-                       uint64_t block_len, uint64_t row_start,
-                       dev_block *out) {
-  const obx_micro_header *h = (const obx_micro_header *)block;
-  if (h->magic != OBX_MICRO_BLOCK_MAGIC) return OBX_INVALID_ARGUMENT;
-  if (h->column_count != n_cols) return OBX_INVALID_ARGUMENT;
-  if (h->data_zlength > (int64_t)block_len ||
-      h->data_zlength < OBX_MICRO_HEADER_SIZE)
-    return OBX_INVALID_ARGUMENT;
-  if ((int64_t)host_crc32c(block + OBX_MICRO_HEADER_SIZE,
-                           (int64_t)h->data_zlength - OBX_MICRO_HEADER_SIZE) !=
-      h->data_checksum)
-    return OBX_PHYSIC_CHECKSUM_ERROR;
-  memset(out, 0, sizeof(*out));
-  out->row_start_lo = (uint32_t)row_start;
-  out->row_start_hi = (uint32_t)(row_start >> 32);
-  out->row_count = h->row_count;
-  out->block_len = (uint32_t)block_len;
-  out->block_byte = dev_off;
-  const uint64_t meta_base =
-      dev_off + h->header_size + (uint64_t)n_cols * sizeof(obx_col_header);
-  const obx_col_header *chp =
-      (const obx_col_header *)(block + h->header_size);
-  const uint8_t *meta_host = block + h->header_size +
-                             (uint64_t)n_cols * sizeof(obx_col_header);
-  const uint8_t evb = obx_hdr_extend_value_bit(h);
-
-  for (uint16_t c = 0; c < n_cols; c++) {
-    const obx_col_header *ch = &chp[c];
-    dev_col *dc = &out->cols[c];
-    const int sc = obx_store_class(ch->obj_type);
-    const int64_t tss = obx_type_store_size(ch->obj_type);
-    dc->enc = (uint8_t)ch->type;
-    dc->datum_len = cols[c].len;
-    dc->tss = (uint8_t)(tss > 0 ? tss : cols[c].len);
-    dc->ext_width = evb;
-    if (sc == OBX_SC_INT) dc->flags |= OBX_DF_SIGNED;
-    if (sc == OBX_SC_STRING) dc->flags |= OBX_DF_STRING;
-    const uint64_t col_base = meta_base + ch->offset;
-    const uint8_t *col_host = meta_host + ch->offset;
-    const int has_ext = (ch->attr & OBX_COL_ATTR_HAS_EXTEND_VALUE) ? 1 : 0;
-    const int bp = (ch->attr & OBX_COL_ATTR_BIT_PACKING) ? 1 : 0;
-
-    switch (ch->type) {
-      case OBX_COL_RAW: {
-        if (bp) dc->flags |= OBX_DF_BITPACK;
-        dc->width = (uint8_t)ch->length;
-        uint64_t ext_bits = has_ext ? (uint64_t)evb * h->row_count : 0;
-        if (has_ext) {
-          dc->flags |= OBX_DF_HAS_EXT;
-          dc->ext_bit = col_base * 8;
-        }
-        if (bp) {
-          dc->data_bit = col_base * 8 + ext_bits;
-        } else {
-          dc->data_bit = (col_base + (ext_bits + 7) / 8) * 8;
-        }
-        break;
-      }
-      case OBX_COL_DICT: {
-        const obx_dict_meta *dm = (const obx_dict_meta *)col_host;
-        if (bp) dc->flags |= OBX_DF_BITPACK;
-        dc->width = dm->row_ref_size;
-        dc->count = dm->count;
-        dc->entry_len = (uint8_t)dm->data_size;
-        dc->dict_byte = col_base + sizeof(obx_dict_meta);
-        dc->data_bit = (col_base + ch->length) * 8; /* refs follow meta */
-        break;
-      }
-      case OBX_COL_RLE: {
-        const obx_rle_meta *rm = (const obx_rle_meta *)col_host;
-        dc->runs = rm->count;
-        dc->rib = rm->attr & 7;
-        dc->rfb = (rm->attr >> 3) & 7;
-        dc->aux_byte = col_base + sizeof(obx_rle_meta);
-        const obx_dict_meta *dm =
-            (const obx_dict_meta *)(col_host + rm->offset);
-        dc->count = dm->count;
-        dc->entry_len = (uint8_t)dm->data_size;
-        dc->dict_byte = col_base + rm->offset + sizeof(obx_dict_meta);
-        break;
-      }
-      case OBX_COL_CONST: {
-        const obx_const_meta *cm = (const obx_const_meta *)col_host;
-        dc->runs = cm->count; /* exception count */
-        dc->rib = cm->attr & 7;
-        dc->rfb = cm->const_ref;
-        if (cm->count == 0) {
-          if (cm->const_ref > 0) {
-            dc->count = 0; /* null-const */
-          } else {
-            dc->count = 1;
-            int64_t cell = (sc == OBX_SC_INT) ? tss : cols[c].len;
-            uint64_t v = 0;
-            memcpy(&v, col_host + cm->offset, (size_t)cell);
-            dc->base = (sc == OBX_SC_INT)
-                           ? (int64_t)obx_sign_extend(v, tss, 1)
-                           : (sc == OBX_SC_DECIMAL
-                                  ? (int64_t)obx_sign_extend(v, cell, 1)
-                                  : (int64_t)v);
-          }
-        } else {
-          dc->aux_byte = col_base + sizeof(obx_const_meta);
-          const obx_dict_meta *dm =
-              (const obx_dict_meta *)(col_host + cm->offset);
-          dc->count = dm->count;
-          dc->entry_len = (uint8_t)dm->data_size;
-          dc->dict_byte = col_base + cm->offset + sizeof(obx_dict_meta);
-        }
-        break;
-      }
-      case OBX_COL_INTEGER_BASE_DIFF: {
-        const obx_intdiff_meta *im = (const obx_intdiff_meta *)col_host;
-        if (bp) dc->flags |= OBX_DF_BITPACK;
-        dc->width = im->length;
-        uint64_t b = 0;
-        memcpy(&b, col_host + sizeof(obx_intdiff_meta), (size_t)tss);
-        dc->base = (int64_t)obx_sign_extend(b, tss, sc == OBX_SC_INT);
-        uint64_t data0 = col_base + ch->length;
-        uint64_t ext_bits = has_ext ? (uint64_t)evb * h->row_count : 0;
-        if (has_ext) {
-          dc->flags |= OBX_DF_HAS_EXT;
-          dc->ext_bit = data0 * 8;
-        }
-        if (bp) dc->data_bit = data0 * 8 + ext_bits;
-        else dc->data_bit = (data0 + (ext_bits + 7) / 8) * 8;
-        break;
-      }
-      case OBX_COL_STRING_PREFIX: {
-        const obx_sprefix_meta *pm = (const obx_sprefix_meta *)col_host;
-        dc->count = pm->count;
-        dc->entry_len = pm->hex_char_cnt;
-        dc->rib = pm->pib;
-        dc->dict_byte = col_base + sizeof(obx_sprefix_meta); /* hex chars */
-        dc->aux_byte = dc->dict_byte + pm->hex_char_cnt;     /* end index */
-        /* fixed cell stride: 1 + max suffix (raw or nibble-packed) */
-        {
-          const uint8_t *ends = col_host + sizeof(obx_sprefix_meta) +
-                                pm->hex_char_cnt;
-          uint64_t prev = 0, min_pl = ~0ull;
-          for (uint32_t j = 0; j < pm->count; j++) {
-            uint64_t e2 = 0;
-            memcpy(&e2, ends + (size_t)j * pm->pib, pm->pib);
-            if (e2 - prev < min_pl) min_pl = e2 - prev;
-            prev = e2;
-          }
-          uint32_t max_suffix = pm->string_size - (uint32_t)min_pl;
-          dc->width = (uint8_t)(1 + (pm->hex_char_cnt
-                                         ? (max_suffix + 1) / 2
-                                         : max_suffix));
-        }
-        uint64_t data0 = col_base + ch->length;
-        uint64_t ext_bits = has_ext ? (uint64_t)evb * h->row_count : 0;
-        if (has_ext) {
-          dc->flags |= OBX_DF_HAS_EXT;
-          dc->ext_bit = data0 * 8;
-        }
-        dc->data_bit = (data0 + (ext_bits + 7) / 8) * 8;
-        break;
-      }
-      case OBX_COL_SUBSTR: {
-        const obx_substr_meta *sm3 = (const obx_substr_meta *)col_host;
-        if (sm3->ref_col >= n_cols) return OBX_INVALID_ARGUMENT;
-        dc->runs = sm3->exc_cnt;
-        dc->rib = sm3->rib;
-        dc->width = (uint8_t)sm3->ref_col; /* ref column index */
-        dc->base = sm3->start_pos;
-        dc->dict_byte = col_base + sizeof(obx_substr_meta); /* exc rids */
-        dc->aux_byte = dc->dict_byte + (uint64_t)sm3->exc_cnt * sm3->rib;
-        break;
-      }
-      case OBX_COL_EQUAL: {
-        const obx_coleq_meta *em = (const obx_coleq_meta *)col_host;
-        if (em->ref_col >= n_cols) return OBX_INVALID_ARGUMENT;
-        dc->runs = em->exc_cnt;
-        dc->rib = em->rib;
-        dc->width = (uint8_t)em->ref_col; /* ref column index */
-        dc->dict_byte = col_base + sizeof(obx_coleq_meta); /* exc row_ids */
-        dc->aux_byte = dc->dict_byte + (uint64_t)em->exc_cnt * em->rib;
-        break;
-      }
-      case OBX_COL_HEX_PACKING: {
-        const obx_hex_meta *hm = (const obx_hex_meta *)col_host;
-        dc->width = (uint8_t)((hm->string_size + 1) / 2); /* row stride B */
-        dc->count = hm->char_cnt;
-        dc->dict_byte = col_base + sizeof(obx_hex_meta); /* char array */
-        uint64_t data0 = col_base + ch->length;
-        uint64_t ext_bits = has_ext ? (uint64_t)evb * h->row_count : 0;
-        if (has_ext) {
-          dc->flags |= OBX_DF_HAS_EXT;
-          dc->ext_bit = data0 * 8;
-        }
-        dc->data_bit = (data0 + (ext_bits + 7) / 8) * 8;
-        break;
-      }
-      case OBX_COL_STRING_DIFF: {
-        const obx_sdiff_meta *sm = (const obx_sdiff_meta *)col_host;
-        dc->runs = sm->diff_desc_cnt;
-        dc->entry_len = sm->hex_char_cnt;
-        dc->dict_byte = col_base + sizeof(obx_sdiff_meta); /* descs */
-        const uint8_t *descs = col_host + sizeof(obx_sdiff_meta);
-        uint32_t diff_len = 0;
-        for (uint32_t i = 0; i < sm->diff_desc_cnt; i++)
-          if (descs[i] & 1) diff_len += descs[i] >> 1;
-        dc->rib = (uint8_t)diff_len;
-        dc->width = (uint8_t)(sm->hex_char_cnt ? (diff_len + 1) / 2
-                                               : diff_len);
-        dc->aux_byte = dc->dict_byte + sm->diff_desc_cnt +
-                       sm->hex_char_cnt; /* common bytes */
-        uint64_t data0 = col_base + ch->length;
-        uint64_t ext_bits = has_ext ? (uint64_t)evb * h->row_count : 0;
-        if (has_ext) {
-          dc->flags |= OBX_DF_HAS_EXT;
-          dc->ext_bit = data0 * 8;
-        }
-        dc->data_bit = (data0 + (ext_bits + 7) / 8) * 8;
-        break;
-      }
-      default:
-        return OBX_NOT_SUPPORTED;
-    }
-  }
-  return OBX_SUCCESS;
-}
-
-int obx_pax_host_load(const obx_blockset *bs, obx_handle &h,
-                      std::vector<dev_block> &blocks) {
-  if (bs->n_cols > OBX_DEV_MAX_COLS) return OBX_NOT_SUPPORTED;
-  for (uint16_t c = 0; c < bs->n_cols; c++) {
-    /* decimal scale bounds the P10 tables (reference: decimal-int
-       precision <= 18 digits on this path) */
-    if (bs->cols[c].scale < 0 || bs->cols[c].scale > 18)
-      return OBX_NOT_SUPPORTED;
-  }
-  h.n_cols = bs->n_cols;
-  h.total_bytes = bs->block_offsets[bs->n_blocks];
-  memcpy(h.cols, bs->cols, sizeof(obx_col_schema) * bs->n_cols);
-  blocks.resize(bs->n_blocks);
-  for (uint32_t b = 0; b < bs->n_blocks; b++) {
-    const uint64_t off = bs->block_offsets[b];
-    int rc = parse_block(bs->cols, bs->n_cols, bs->data + off, off,
-                         bs->block_offsets[b + 1] - off, h.total_rows,
-                         &blocks[b]);
-    if (rc != OBX_SUCCESS) return rc;
-    obx_fold_block(h, blocks[b]);
-  }
-  /* dict stability: identical dict payload in every block enables the
-     JIT's persistent (whole-kernel) histograms/value tables */
-  for (uint16_t c = 0; c < bs->n_cols; c++) {
-    h.col_dict_stable[c] = h.col_dict_any[c];
-    if (!h.col_dict_stable[c]) continue;
-    const dev_col &d0 = blocks[0].cols[c];
-    size_t dlen = (size_t)d0.count * d0.entry_len;
-    for (uint32_t b = 1; b < bs->n_blocks && h.col_dict_stable[c]; b++) {
-      const dev_col &db = blocks[b].cols[c];
-      if (db.count != d0.count || db.entry_len != d0.entry_len ||
-          memcmp(bs->data + db.dict_byte, bs->data + d0.dict_byte, dlen))
-        h.col_dict_stable[c] = false;
-    }
-  }
-  return OBX_SUCCESS;
 }
 
 int obx_finish_load(obx_gpu_ctx *ctx, std::unique_ptr<obx_handle> h,
@@ -533,19 +142,6 @@ int obx_finish_load(obx_gpu_ctx *ctx, std::unique_ptr<obx_handle> h,
   return (int)ctx->handles.size() - 1;
 }
 
-extern "C" int obx_gpu_load_blocks(obx_gpu_ctx *ctx, const obx_blockset *bs) {
-  if (!ctx || !bs) return OBX_INVALID_ARGUMENT;
-  auto h = std::make_unique<obx_handle>();
-  std::vector<dev_block> blocks;
-  int rc = obx_pax_host_load(bs, *h, blocks);
-  if (rc != OBX_SUCCESS) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMalloc(&h->d_buf, h->total_bytes + 64));
-  HIP_TRY(hipMemset(h->d_buf + h->total_bytes, 0, 64));
-  HIP_TRY(hipMemcpy(h->d_buf, bs->data, h->total_bytes, hipMemcpyHostToDevice));
-  return obx_finish_load(ctx, std::move(h), blocks);
-}
-
 extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
   if (!obx_handle_lookup(ctx, handle)) return OBX_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -553,234 +149,10 @@ extern "C" int obx_gpu_free_blocks(obx_gpu_ctx *ctx, int handle) {
   return OBX_SUCCESS;
 }
 
-/* build plan header + device leaves (pure: no HIP calls). ctx resolves the
-   set ids of IN_SET leaves; the GPU-free probes pass none, and such a leaf
-   is then an unknown id. */
-static int build_plan(const obx_gpu_ctx *ctx, const obx_handle &h,
-                      const obx_filter_desc *filter, const obx_agg_desc *agg,
-                      dev_plan_hdr &ph, dev_leaf pl[OBX_DEV_MAX_LEAVES]) {
-  memset(&ph, 0, sizeof(ph));
-  memset(pl, 0, sizeof(dev_leaf) * OBX_DEV_MAX_LEAVES);
-  uint16_t nl = filter ? filter->n_leaves : 0;
-  if (nl > OBX_DEV_MAX_LEAVES) return OBX_INVALID_ARGUMENT;
-  ph.n_leaves = nl;
-  if (filter && filter->n_prog) {
-    /* validate the combine program (operand range, stack discipline) */
-    int sp = 0;
-    for (int p = 0; p < filter->n_prog; p++) {
-      uint8_t t = filter->prog[p];
-      if (t < nl) sp++;
-      else if ((t == OBX_TOK_AND || t == OBX_TOK_OR) && sp >= 2) sp--;
-      else return OBX_INVALID_ARGUMENT;
-      if (sp > 8) return OBX_INVALID_ARGUMENT;
-    }
-    if (sp != 1) return OBX_INVALID_ARGUMENT;
-    ph.n_prog = filter->n_prog;
-    memcpy(ph.prog, filter->prog, filter->n_prog);
-  }
-  for (uint16_t i = 0; i < nl; i++) {
-    const obx_filter_leaf *lf = &filter->leaves[i];
-    if (lf->col >= h.n_cols) return OBX_INVALID_ARGUMENT;
-    if (lf->op > OBX_OP_IN_SET) return OBX_INVALID_ARGUMENT;
-    pl[i].col = lf->col;
-    pl[i].op = lf->op;
-    if (lf->op == OBX_OP_IN_SET) {
-      /* the set's device view rides in the leaf's in_list words; keys
-         compare as decoded datums, so no char order map */
-      const obx_keyset *ks = obx_keyset_lookup(ctx, lf->lo);
-      if (!ks) return OBX_INVALID_ARGUMENT;
-      obx_keyset_to_leaf(ks->view, pl[i].in_list);
-      continue;
-    }
-    pl[i].vlo = lf->lo;
-    pl[i].vhi = lf->hi;
-    pl[i].n_in = lf->n_in;
-    for (int j = 0; j < lf->n_in && j < 8; j++) pl[i].in_list[j] = lf->in_list[j];
-    if (lf->op == OBX_OP_BLACK) {
-      /* stack-discipline validation mirroring the oracle's
-         obx__bprog_valid */
-      if (lf->n_bprog == 0 || lf->n_bprog > OBX_BX_MAX_PROG ||
-          lf->n_bcols == 0 || lf->n_bcols > OBX_BX_MAX_COLS)
-        return OBX_INVALID_ARGUMENT;
-      int sp = 0;
-      for (int p = 0; p < lf->n_bprog; p++) {
-        uint8_t op2 = lf->bprog[p];
-        if (op2 < 0x40) {
-          if (op2 >= lf->n_bcols) return OBX_INVALID_ARGUMENT;
-          sp++;
-        } else if (op2 < 0x50) {
-          if ((op2 & 0x0F) >= OBX_BX_MAX_CONST) return OBX_INVALID_ARGUMENT;
-          sp++;
-        } else if (op2 == 0x54 || op2 == 0x72) {
-          if (sp < 1) return OBX_INVALID_ARGUMENT;
-        } else if ((op2 >= 0x50 && op2 <= 0x53) || op2 == 0x55 ||
-                   (op2 >= 0x60 && op2 <= 0x65) || op2 == 0x70 ||
-                   op2 == 0x71) {
-          if (sp < 2) return OBX_INVALID_ARGUMENT;
-          sp--;
-        } else {
-          return OBX_INVALID_ARGUMENT;
-        }
-        if (sp > 8) return OBX_INVALID_ARGUMENT;
-      }
-      if (sp != 1) return OBX_INVALID_ARGUMENT;
-      for (int j = 0; j < lf->n_bcols; j++) {
-        if (lf->bcols[j] >= h.n_cols) return OBX_INVALID_ARGUMENT;
-        pl[i].bcols[j] = lf->bcols[j];
-      }
-      pl[i].n_bcols = lf->n_bcols;
-      pl[i].n_bprog = lf->n_bprog;
-      memcpy(pl[i].bprog, lf->bprog, lf->n_bprog);
-      memcpy(pl[i].bconst, lf->bconst, sizeof(pl[i].bconst));
-      pl[i].col = lf->bcols[0]; /* pruning/lowering anchor */
-      continue;
-    }
-    /* char columns compare byte-lexicographically: order-map the operands
-       exactly like the oracle's char_key (low len LE bytes -> BE int) */
-    if (obx_store_class(h.cols[lf->col].obj_type) == OBX_SC_STRING) {
-      uint32_t len = h.cols[lf->col].len;
-      auto ck = [len](int64_t x) -> int64_t {
-        return (int64_t)(__builtin_bswap64((uint64_t)x) >> (8 * (8 - len)));
-      };
-      pl[i].char_len = (uint8_t)len;
-      pl[i].vlo = ck(lf->lo);
-      pl[i].vhi = ck(lf->hi);
-      for (int j = 0; j < lf->n_in && j < 8; j++)
-        pl[i].in_list[j] = ck(lf->in_list[j]);
-    }
-  }
-  /* AND-only plans: merge a lower-bound and an upper-bound leaf on the
-     same column into one OP_BT leaf (the reference's range-node build,
-     ObWhiteFilterExecutor; one pass instead of two in the kernels) */
-  if (filter && !filter->n_prog && nl > 1) {
-    for (uint16_t i = 0; i < nl; i++) {
-      if (pl[i].op != OBX_OP_GE && pl[i].op != OBX_OP_GT) continue;
-      for (uint16_t k = 0; k < nl; k++) {
-        if (k == i || pl[k].col != pl[i].col) continue;
-        if (pl[k].op != OBX_OP_LE && pl[k].op != OBX_OP_LT) continue;
-        int64_t lo = pl[i].vlo, hi = pl[k].vlo;
-        if (pl[i].op == OBX_OP_GT) {
-          if (lo == INT64_MAX) continue;
-          lo++;
-        }
-        if (pl[k].op == OBX_OP_LT) {
-          if (hi == INT64_MIN) continue;
-          hi--;
-        }
-        pl[i].op = OBX_OP_BT;
-        pl[i].vlo = lo;
-        pl[i].vhi = hi;
-        /* drop leaf k */
-        for (uint16_t m = k; m + 1 < nl; m++) pl[m] = pl[m + 1];
-        nl--;
-        ph.n_leaves = nl;
-        if (k < i) i--;
-        i--; /* re-examine the merged leaf (another pair may exist) */
-        break;
-      }
-    }
-  }
-
-  /* resolve needed value slots */
-  int slot_of_col[64];
-  for (int i = 0; i < 64; i++) slot_of_col[i] = -1;
-  auto need = [&](uint16_t c) -> uint8_t {
-    if (slot_of_col[c] < 0) {
-      if (ph.n_need >= OBX_DEV_MAX_NEED) return 0xFF;
-      slot_of_col[c] = ph.n_need;
-      ph.need_cols[ph.n_need++] = c;
-    }
-    return (uint8_t)slot_of_col[c];
-  };
-  if (agg) {
-    if (agg->n_group_cols > 2 || agg->n_aggs > OBX_DEV_MAX_AGGS)
-      return OBX_INVALID_ARGUMENT;
-    ph.n_group_cols = agg->n_group_cols;
-    for (int g = 0; g < agg->n_group_cols; g++) {
-      if (agg->group_cols[g] >= h.n_cols) return OBX_INVALID_ARGUMENT;
-      ph.group_idx[g] = need(agg->group_cols[g]);
-      ph.group_len[g] = h.cols[agg->group_cols[g]].len;
-    }
-    ph.n_aggs = agg->n_aggs;
-    for (int a = 0; a < agg->n_aggs; a++) {
-      const obx_agg_expr *e = &agg->aggs[a];
-      dev_agg *da = &ph.aggs[a];
-      da->kind = e->kind;
-      da->ia = da->ib = da->ic = 0xFF;
-      if (e->col_a != UINT16_MAX && e->col_a >= h.n_cols)
-        return OBX_INVALID_ARGUMENT;
-      if (e->col_a != UINT16_MAX) da->ia = need(e->col_a);
-      if (e->kind == OBX_AGG_SUM_PROD2 || e->kind == OBX_AGG_SUM_PROD3 ||
-          e->kind == OBX_AGG_SUM_MUL) {
-        if (e->col_b >= h.n_cols) return OBX_INVALID_ARGUMENT;
-        da->ib = need(e->col_b);
-        static const int64_t P10[19] = {1ll,10ll,100ll,1000ll,10000ll,
-          100000ll,1000000ll,10000000ll,100000000ll,1000000000ll,
-          10000000000ll,100000000000ll,1000000000000ll,10000000000000ll,
-          100000000000000ll,1000000000000000ll,10000000000000000ll,
-          100000000000000000ll,1000000000000000000ll};
-        da->one_b = P10[h.cols[e->col_b].scale];
-        if (e->kind == OBX_AGG_SUM_PROD3) {
-          if (e->col_c >= h.n_cols) return OBX_INVALID_ARGUMENT;
-          da->ic = need(e->col_c);
-          da->one_c = P10[h.cols[e->col_c].scale];
-        }
-      }
-    }
-    /* group keys decode via col_value (no block context): COLUMN_EQUAL
-       group columns would misdecode — reject them (value/filter columns
-       on COLUMN_EQUAL are fully supported via col_value2) */
-    for (uint32_t g = 0; g < ph.n_group_cols; g++)
-      if (h.col_span_any[ph.need_cols[ph.group_idx[g]]])
-        return OBX_NOT_SUPPORTED;
-  }
-  /* group aggregates into row passes: aggs whose inputs fit in <=3 shared
-     decoded columns run together (COUNT(*) needs no pass — filled from the
-     group counts at flush) */
-  if (agg) {
-    bool used[OBX_DEV_MAX_AGGS] = {};
-    ph.n_passes = 0;
-    for (int a = 0; a < agg->n_aggs; a++) {
-      if (used[a]) continue;
-      const dev_agg *da = &ph.aggs[a];
-      if (da->kind == OBX_AGG_COUNT && da->ia == 0xFF) { used[a] = true; continue; }
-      dev_pass *pp = &ph.passes[ph.n_passes++];
-      memset(pp, 0, sizeof(*pp));
-      auto col_sel = [&](uint8_t need_idx) -> int {
-        if (need_idx == 0xFF) return -1;
-        for (int k = 0; k < pp->n_cols; k++)
-          if (pp->cols[k] == need_idx) return k;
-        if (pp->n_cols >= 3) return -2; /* no room */
-        pp->cols[pp->n_cols] = need_idx;
-        return pp->n_cols++;
-      };
-      auto try_add = [&](int idx) -> bool {
-        const dev_agg *d = &ph.aggs[idx];
-        uint8_t save_n = pp->n_cols;
-        int sa = col_sel(d->ia), sb = col_sel(d->ib), sc = col_sel(d->ic);
-        if (sa == -2 || sb == -2 || sc == -2) { pp->n_cols = save_n; return false; }
-        dev_pass_agg *pa = &pp->aggs[pp->n_aggs++];
-        pa->kind = d->kind;
-        pa->agg_idx = (uint8_t)idx;
-        pa->sa = (uint8_t)(sa < 0 ? 0xFF : sa);
-        pa->sb = (uint8_t)(sb < 0 ? 0xFF : sb);
-        pa->sc = (uint8_t)(sc < 0 ? 0xFF : sc);
-        pa->one_b = d->one_b;
-        pa->one_c = d->one_c;
-        return true;
-      };
-      try_add(a);
-      used[a] = true;
-      for (int b2 = a + 1; b2 < agg->n_aggs; b2++) {
-        if (used[b2]) continue;
-        const dev_agg *d2 = &ph.aggs[b2];
-        if (d2->kind == OBX_AGG_COUNT && d2->ia == 0xFF) { used[b2] = true; continue; }
-        if (try_add(b2)) used[b2] = true;
-      }
-    }
-  }
-
-  return OBX_SUCCESS;
+/* build_plan's resolver: the device view of one of the context's key sets */
+static const obx_keyset_dev *set_view_of(const void *ctx, int64_t set_id) {
+  const obx_keyset *ks = obx_keyset_lookup((const obx_gpu_ctx *)ctx, set_id);
+  return ks ? &ks->view : nullptr;
 }
 
 /* build the plan + upload leaves + lower per-block tests on device */
@@ -788,7 +160,7 @@ static int prep_query(obx_gpu_ctx *ctx, obx_handle &h,
                       const obx_filter_desc *filter, const obx_agg_desc *agg,
                       dev_plan_hdr &ph, dev_leaf *pl_out = nullptr) {
   dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(ctx, h, filter, agg, ph, pl);
+  int rc = build_plan(set_view_of, ctx, h, filter, agg, ph, pl);
   if (pl_out) memcpy(pl_out, pl, sizeof(pl));
   if (rc != OBX_SUCCESS) return rc;
   uint16_t nl = ph.n_leaves;
@@ -853,8 +225,6 @@ static const obx_bdesc *bdesc_get(obx_handle &h, const obx_bdesc_cols &cols,
   return victim->d;
 }
 
-#include "obx_jit.inc"
-
 /* the plan-generic filter kernel: LDS-staged when every block fits the
    stage, the _prog build when the plan carries a combine program */
 static decltype(&k_filter) generic_filter_kernel(const obx_handle &h,
@@ -916,7 +286,8 @@ static int run_filter(obx_gpu_ctx *ctx, obx_handle &h,
   HIP_TRY(hipMemsetAsync(h.d_counters, 0, 16 * 8, ctx->stream));
   /* bitmap-only filters take the specialized wave-per-block kernel
      (direct global reads of just the leaf streams; obx_jit_filter.inc) */
-  jit_entry *fje = jit_prepare_filter(h, ph, plv, want_row_ids);
+  const jit_entry *fje =
+      jit_prepare_filter(ctx->device, h, ph, plv, want_row_ids);
   ctx->last_jit = fje ? 2 : 0;
   HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
   if (fje) {
@@ -1552,9 +923,9 @@ extern "C" int obx_gpu_scan_filter_agg(obx_gpu_ctx *ctx, int handle,
     }
   } else {
     /* plan-specialized JIT kernel when eligible (compiled once per plan
-       signature, before the timed region; obx_jit.inc) */
-    jit_entry *je = jit_prepare(h, ph, plv);
-    ctx->last_jit = je ? g_jit_kind : 0; /* 2 = persistent v2, 1 = v1 */
+       signature, before the timed region; obx_jit_rt.cpp) */
+    const jit_entry *je = jit_prepare(ctx->device, h, ph, plv);
+    ctx->last_jit = je ? je->kind : 0; /* 2 = persistent v2, 1 = v1 */
     const obx_bdesc *bd = nullptr;
     if (je && je->bdesc) {
       /* the first query with this column list pays the build: its device
@@ -1780,133 +1151,6 @@ extern "C" int obx_gpu_group_hash_host_model(
                                                 : OBX_SUCCESS;
 }
 
-extern "C" uint64_t obx_crc32c(const uint8_t *buf, int64_t len) {
-  return host_crc32c(buf, len);
-}
-
-/* Debug/test-only: generate the hipRTC source the JIT would compile for a
- * plan against synthetic load-time column summaries, without a GPU (the
- * container has no device; tests hipcc-compile the dump offline).
- * col_flags bits: 1 = dict-everywhere, 2 = ext-any, 4 = bounds known.
- * Returns the source length (>= 0) or a negative status; 0 = the plan
- * would not take the JIT path. The _ex form also takes the block count and
- * the device's CU count (0 = default), which size the launch grid and with
- * it the i64 accumulator bound; a v2 source reports that grid in
- * *grid_out. */
-extern "C" int64_t obx_jit_dump_src_ex(
-    const obx_filter_desc *filter, const obx_agg_desc *agg,
-    const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_flags,
-    const int64_t *col_min, const int64_t *col_max,
-    const uint32_t *col_maxcnt, const uint32_t *col_maxw,
-    uint32_t max_block_rows, int force_v1, uint32_t n_blocks, uint32_t n_cus,
-    uint32_t *grid_out, char *out, int64_t cap) {
-  if (!cols || n_cols > OBX_DEV_MAX_COLS) return OBX_INVALID_ARGUMENT;
-  if (grid_out) *grid_out = 0;
-  /* no context here to resolve a set id: such a plan renders nothing */
-  for (uint16_t i = 0; filter && i < filter->n_leaves && i < 8; i++)
-    if (filter->leaves[i].op == OBX_OP_IN_SET) return 0;
-  obx_handle h;
-  h.n_cols = n_cols;
-  h.n_blocks = n_blocks ? n_blocks : 1;
-  if (n_cus) h.n_cus = n_cus;
-  h.max_block_rows = max_block_rows ? max_block_rows : 4096;
-  h.max_block_len = OBX_LDS_STAGE_BYTES - 32;
-  memcpy(h.cols, cols, sizeof(obx_col_schema) * n_cols);
-  for (uint16_t c = 0; c < n_cols; c++) {
-    h.col_dict_every[c] = (col_flags[c] & 1) != 0;
-    h.col_ext_any[c] = (col_flags[c] & 2) != 0;
-    h.col_known[c] = (col_flags[c] & 4) != 0;
-    h.col_raw8_every[c] = (col_flags[c] & 8) != 0;
-    h.col_rangefam_every[c] = (col_flags[c] & 16) != 0;
-    h.col_dict_any[c] = h.col_dict_every[c] ||
-        (obx_store_class(cols[c].obj_type) == OBX_SC_STRING &&
-         (col_flags[c] & 1));
-    h.col_dict_stable[c] = (col_flags[c] & 32) != 0 && h.col_dict_any[c];
-    h.col_min[c] = col_min[c];
-    h.col_max[c] = col_max[c];
-    h.col_maxcnt[c] = col_maxcnt[c];
-    h.col_maxw[c] = col_maxw ? col_maxw[c] : 255;
-    /* a maximum count past an obx_bdesc slot: some block does not fit */
-    h.col_bdesc_unfit[c] = col_maxcnt[c] > 0xFFFFu;
-    uint8_t cls = h.col_dict_every[c] ? 1 : 0;
-    if (obx_store_class(cols[c].obj_type) == OBX_SC_STRING) cls |= 0x10;
-    h.col_class.push_back(cls);
-    h.col_cnt.push_back(
-        (uint8_t)(h.col_maxcnt[c] > 254 ? 255 : h.col_maxcnt[c]));
-  }
-  summarize_col_classes(h); /* one synthetic block stands for all */
-  dev_plan_hdr ph;
-  dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(nullptr, h, filter, agg, ph, pl);
-  if (rc != OBX_SUCCESS) return rc;
-  if (!agg) { /* bitmap-filter path: dump the wave-per-block filter JIT */
-    jit_fstrategy fst;
-    if (!jit_build_fstrategy(h, ph, pl, fst)) return 0;
-    if (getenv("OBX_DUMP_RID") && fst.fstage) { /* test hook */
-      fst.frid = 1;
-      fst.fnch = (uint16_t)((h.max_block_rows + 63) / 64);
-    }
-    std::string fsrc = jit_gen_source_filter(ph, fst);
-    if (out && cap > (int64_t)fsrc.size()) {
-      memcpy(out, fsrc.data(), fsrc.size());
-      out[fsrc.size()] = 0;
-    }
-    return (int64_t)fsrc.size();
-  }
-  jit_scan_choice c;
-  if (!jit_scan_choose(h, ph, pl, force_v1 != 0, c)) return 0;
-  if (c.kind == 2 && grid_out)
-    *grid_out = jit_grid_for(h.n_blocks, h.n_cus, c.st.wpb);
-  std::string src = jit_scan_source(ph, c);
-  if (out && cap > (int64_t)src.size()) {
-    memcpy(out, src.data(), src.size());
-    out[src.size()] = 0;
-  }
-  return (int64_t)src.size();
-}
-
-extern "C" int64_t obx_jit_dump_src(
-    const obx_filter_desc *filter, const obx_agg_desc *agg,
-    const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_flags,
-    const int64_t *col_min, const int64_t *col_max,
-    const uint32_t *col_maxcnt, const uint32_t *col_maxw,
-    uint32_t max_block_rows, int force_v1,
-    char *out, int64_t cap) {
-  return obx_jit_dump_src_ex(filter, agg, cols, n_cols, col_flags, col_min,
-                             col_max, col_maxcnt, col_maxw, max_block_rows,
-                             force_v1, 1, 0, nullptr, out, cap);
-}
-
-/* Debug/test-only: the plan and JIT-eligibility decisions for synthetic
- * per-(block,col) class / dict-count arrays (n_blocks x n_cols, the layout
- * of obx_handle::col_class / col_cnt), without a GPU. Returns build_plan's
- * status when it is not OBX_SUCCESS, else 1 if the plan passes
- * jit_plan_shape + jit_blocks_ok and 0 if not. */
-extern "C" int obx_jit_probe_blocks(
-    const obx_filter_desc *filter, const obx_agg_desc *agg,
-    const obx_col_schema *cols, uint16_t n_cols, const uint8_t *col_class,
-    const uint8_t *col_cnt, uint32_t n_blocks) {
-  if (!cols || !col_class || !col_cnt || n_cols > OBX_DEV_MAX_COLS)
-    return OBX_INVALID_ARGUMENT;
-  obx_handle h;
-  h.n_cols = n_cols;
-  h.n_blocks = n_blocks;
-  memcpy(h.cols, cols, sizeof(obx_col_schema) * n_cols);
-  for (size_t b = 0; b < n_blocks; b++) {
-    h.col_class.insert(h.col_class.end(), col_class + b * n_cols,
-                       col_class + (b + 1) * n_cols);
-    h.col_cnt.insert(h.col_cnt.end(), col_cnt + b * n_cols,
-                     col_cnt + (b + 1) * n_cols);
-    summarize_col_classes(h);
-  }
-  dev_plan_hdr ph;
-  dev_leaf pl[OBX_DEV_MAX_LEAVES];
-  int rc = build_plan(nullptr, h, filter, agg, ph, pl);
-  if (rc != OBX_SUCCESS) return rc;
-  jit_shape js;
-  return jit_plan_shape(ph, js) && jit_blocks_ok(h, ph, js) ? 1 : 0;
-}
-
 /* Debug/test-only: the load-time facts of a blockset, without a GPU. Runs
  * only the host half of the PAX (is_cs == 0) or CS loader, then writes
  * handle_out[7] = n_blocks, n_cols, total_rows, total_bytes, lds_ok,
@@ -1917,7 +1161,7 @@ extern "C" int obx_jit_probe_blocks(
 extern "C" int obx_probe_load_facts(const obx_blockset *bs, int is_cs,
                                     uint64_t *handle_out, uint32_t *col_out) {
   if (!bs || !handle_out || !col_out) return OBX_INVALID_ARGUMENT;
-  obx_handle h;
+  obx_table_facts h;
   std::vector<dev_block> blocks;
   int rc = is_cs ? obx_cs_host_load(bs, h, blocks, nullptr)
                  : obx_pax_host_load(bs, h, blocks);

@@ -1,8 +1,11 @@
 /*
- * obx_host.h — what the two host translation units share (obx_engine.cpp,
- * obx_cs_load.cpp): the kernel entry points, the loaded-table handle and its
- * context, and the load steps both loaders run. Private to csrc/; the public
- * C-ABI is include/obx.h.
+ * obx_host.h — what the host translation units that call HIP share
+ * (obx_engine.cpp, obx_pax_load.cpp, obx_cs_load.cpp, obx_jit_rt.cpp and the
+ * host halves of the .hip files): the kernel entry points, the loaded-table
+ * handle and its context, the load steps both loaders run, and the hipRTC
+ * half of the JIT. The HIP-free units (obx_plan.cpp, obx_jit_gen.cpp,
+ * obx_probes.cpp) see obx_facts.h and obx_jit.h only. Private to csrc/; the
+ * public C-ABI is include/obx.h.
  */
 #ifndef OBX_HOST_H_
 #define OBX_HOST_H_
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "obx_dev.h"
+#include "obx_facts.h"
 #include "obx_grouphash.h"
 #include "obx_keymap.h"
 #include "obx_keyset.h"
@@ -188,10 +192,12 @@ struct dev_tmp {
   ~dev_tmp() { if (p) (void)hipFree(p); }
 };
 
-/* One loaded table. Owns every device pointer below: ~obx_handle is the one
-   place they are released, so a handle is never copied and lives behind a
+/* One loaded table: its load-time facts (obx_facts.h; all the plan builder
+   and the JIT generators see of it) and, below, its device resources and
+   results. Owns every device pointer below: ~obx_handle is the one place
+   they are released, so a handle is never copied and lives behind a
    unique_ptr from the loader's first allocation to free / close. */
-struct obx_handle {
+struct obx_handle : obx_table_facts {
   obx_handle() = default;
   obx_handle(const obx_handle &) = delete;
   obx_handle &operator=(const obx_handle &) = delete;
@@ -199,11 +205,6 @@ struct obx_handle {
 
   uint8_t *d_buf = nullptr;
   dev_block *d_blocks = nullptr;
-  uint32_t n_blocks = 0;
-  uint16_t n_cols = 0;
-  uint64_t total_rows = 0;
-  uint64_t total_bytes = 0;
-  obx_col_schema cols[OBX_DEV_MAX_COLS];
   /* query scratch */
   blk_leaf *d_bleaves = nullptr;
   uint32_t bleaves_cap = 0; /* in (block,leaf) entries */
@@ -248,54 +249,6 @@ struct obx_handle {
   uint64_t sel_rows = 0;
   std::vector<obx_group_row> last_rows; /* full sorted group rows of the
                                            last scan (obx_gpu_agg_fetch) */
-  uint32_t n_cus = 256; /* compute units of the owning device */
-
-  /* ---- load-time facts (obx_fold_block, once per block) ---------------
-     everything the per-query plan and JIT eligibility tests ask of the
-     blocks, so a query costs O(columns), not O(blocks) */
-  bool lds_ok = true;    /* all blocks 16-B aligned and <= LDS stage size */
-  uint32_t max_block_rows = 0;
-  uint32_t max_block_len = 0;
-  /* per-(block,col) encoding summary: low nibble = decode class (0 raw,
-     1 dict, 2 intdiff, 3 const, 4 slow, 5 span), bit4 = string; col_cnt =
-     dict count capped at 255. Kept for the exact per-block cell product of
-     a two-column grouping (jit_pair_cells_max, obx_jit.inc) */
-  std::vector<uint8_t> col_class, col_cnt;
-  bool col_span_any[OBX_DEV_MAX_COLS] = {};    /* class 5 in any block */
-  bool col_grp16_every[OBX_DEV_MAX_COLS] = {}; /* class 1 and count < 16 in
-                                                  every block */
-  bool col_slow_any[OBX_DEV_MAX_COLS] = {};    /* class > 3 or string in
-                                                  any block */
-  uint32_t col_cnt_max[OBX_DEV_MAX_COLS] = {}; /* max of col_cnt */
-  /* max over blocks of (cnt[c0]+1)*(cnt[c1]+1), filled on the first query
-     that groups by (c0, c1) and whose product of column maxima exceeds the
-     16-cell limit (key = c0 << 16 | c1) */
-  mutable std::map<uint32_t, uint32_t> pair_cells_max;
-  bool col_dict_every[OBX_DEV_MAX_COLS] = {}; /* class==1, not string, and
-                                                 count<=63 in every block */
-  bool col_dict_any[OBX_DEV_MAX_COLS] = {};   /* dict (incl. char) with
-                                                 count<=63 in every block */
-  bool col_dict_stable[OBX_DEV_MAX_COLS] = {}; /* dict_any AND the dict
-                                                  payload is byte-identical
-                                                  in every block (group/ref
-                                                  persistence; numeric-only
-                                                  uses additionally require
-                                                  col_dict_every). PAX only */
-  bool col_ext_any[OBX_DEV_MAX_COLS] = {};  /* HAS_EXT in any block */
-  bool col_raw8_every[OBX_DEV_MAX_COLS] = {}; /* 8-B RAW, 64-bit-aligned,
-                                                 no ext, in every block */
-  bool col_rangefam_every[OBX_DEV_MAX_COLS] = {}; /* RAW numeric / INTDIFF
-                                                     (packed-range lowerable)
-                                                     in every block */
-  uint32_t col_maxcnt[OBX_DEV_MAX_COLS] = {}; /* max dict count, uncapped */
-  uint32_t col_maxw[OBX_DEV_MAX_COLS] = {};   /* max packed width (bits)
-                                                 across blocks; 255 = no
-                                                 packed stream (slow enc) */
-  bool col_bdesc_unfit[OBX_DEV_MAX_COLS] = {}; /* a count or width of some
-                                                  block does not fit an
-                                                  obx_bdesc slot: plans that
-                                                  read the column keep the
-                                                  dev_block path */
 
   /* packed per-block descriptors of the persistent scan JIT, one array of
      n_blocks records per ordered column list, built by the first query
@@ -310,13 +263,9 @@ struct obx_handle {
   uint64_t bdesc_builds = 0;
 
   /* stored skip index: per-(block,col) [min,max] of non-null decoded
-     values, captured by k_col_minmax at load (device copy feeds
-     k_lower_leaves pruning; host summary feeds the JIT's i64-accumulator
-     range eligibility, obx_jit.inc) */
+     values, captured by k_col_minmax at load (feeds k_lower_leaves pruning;
+     its host summary is obx_table_facts::col_min / col_max / col_known) */
   int64_t *d_minmax = nullptr;
-  int64_t col_min[OBX_DEV_MAX_COLS] = {};   /* global over blocks */
-  int64_t col_max[OBX_DEV_MAX_COLS] = {};
-  bool col_known[OBX_DEV_MAX_COLS] = {};    /* bounds known in EVERY block */
 };
 
 /* One device-resident key set (obx_keyset.h). Owns its table; lives behind a
@@ -392,13 +341,12 @@ static inline uint32_t grid_for(uint32_t n_blocks) {
   return g ? g : 1;
 }
 
-/* ---- loading: host half, arena upload, finish (obx_engine.cpp) ----------
-   A loader parses its format into dev_blocks without a HIP call, folding
-   each into the handle's facts; uploads h->d_buf in its own way (PAX: a
-   copy, CS: k_cs_decode); and hands the handle to obx_finish_load. */
-
-/* fold one parsed block into every per-column and per-handle fact */
-void obx_fold_block(obx_handle &h, const dev_block &db);
+/* ---- loading: host half, arena upload, finish ---------------------------
+   A loader (obx_pax_load.cpp, obx_cs_load.cpp) parses its format into
+   dev_blocks without a HIP call, folding each into the handle's facts
+   (obx_fold_block, obx_plan.cpp); uploads h->d_buf in its own way (PAX: a
+   copy, CS: k_cs_decode); and hands the handle to obx_finish_load
+   (obx_engine.cpp). */
 
 /* upload the descriptors, allocate the query scratch, capture the min/max
    skip index, and publish the handle: returns its id, or a negative status
@@ -407,11 +355,36 @@ int obx_finish_load(obx_gpu_ctx *ctx, std::unique_ptr<obx_handle> h,
                     const std::vector<dev_block> &blocks);
 
 /* the loaders' host halves: schema checks + parse + fold, no HIP call */
-int obx_pax_host_load(const obx_blockset *bs, obx_handle &h,
+int obx_pax_host_load(const obx_blockset *bs, obx_table_facts &h,
                       std::vector<dev_block> &blocks);
 struct obx_cs_plan; /* device decode tasks (obx_cs_load.cpp) */
-int obx_cs_host_load(const obx_blockset *bs, obx_handle &h,
+int obx_cs_host_load(const obx_blockset *bs, obx_table_facts &h,
                      std::vector<dev_block> &blocks,
                      obx_cs_plan *plan /* null: facts only */);
+
+/* ---- the hipRTC half of the JIT (obx_jit_rt.cpp) ------------------------
+   What a verb holds of a generated kernel. Entries belong to the process-wide
+   compile cache and are never changed or released once made, so the pointer
+   stays good for the life of the process. The generators and everything
+   HIP-free about them are in obx_jit.h. */
+struct jit_entry {
+  hipModule_t mod = nullptr;
+  hipFunction_t fn = nullptr;
+  int kind = 0; /* scan: 1 = v1 generator, 2 = v2 (persistent) */
+  int wpb = 0; /* v2: workgroups per CU the launch grid is sized to */
+  bool bdesc = false;        /* v2: reads the packed block descriptors ... */
+  obx_bdesc_cols bd_cols = {}; /* ... of this ordered column list */
+  int joint = 0;             /* v2: joint-table form (obx_gpu_last_joint) */
+};
+
+/* prepare (compile/lookup) before the timed region, for the device the
+   caller made current; nullptr = use the precompiled kernels */
+const jit_entry *jit_prepare(int device, const obx_table_facts &h,
+                             const dev_plan_hdr &ph, const dev_leaf *pl);
+const jit_entry *jit_prepare_filter(int device, const obx_table_facts &h,
+                                    const dev_plan_hdr &ph, const dev_leaf *pl,
+                                    int want_row_ids);
+int jit_launch(const jit_entry *je, obx_handle &h, const obx_bdesc *bd,
+               hipStream_t stream, uint32_t *grid_out);
 
 #endif /* OBX_HOST_H_ */

@@ -1,6 +1,6 @@
 /*
  * obx_jit_filter.inc — filter-only codegen (obx_gpu_filter): strategy,
- * strategy signature, source (included by obx_jit.inc).
+ * strategy signature, source (included by obx_jit_gen.cpp).
  *
  * Eligibility: one to four leaves, each packed-range or dict-mask (the
  * classes of the scan kernel's inline filter), or a key-set leaf (IN_SET) on
@@ -21,28 +21,13 @@
  * Layout: jit_build_fstrategy (the only place that reads the environment),
  * jit_fstrategy_sig, the fragments both modes share (combine-program fold,
  * stream and operand names per mode; the row tests themselves are in
- * obx_jit.inc), then the phases (plan, strategy, out): prologue; staged
+ * obx_jit_gen.cpp), then the phases (plan, strategy, out): prologue; staged
  * parameters, sweep and kernel; direct kernel. jit_gen_source_filter lists
  * them.
  */
 
-struct jit_fstrategy {
-  uint8_t leaf_kind[4] = {};  /* JL_RANGE, JL_MASK, or JL_SET: key set on a
-                                 packed-range column */
-  uint8_t leaf_form[4] = {};  /* JL_SET: OBX_KS_* form of the set */
-  uint16_t leaf_cols[4] = {};
-  uint8_t leaf_multi[4] = {}; /* r entries per packed read */
-  uint8_t r = 1;              /* rows per lane (strip mining) */
-  uint8_t nslice = 1;         /* direct mode: row slices per block */
-  uint8_t fu = 4;             /* direct mode: pipelined tiles */
-  uint8_t fstage = 0;         /* LDS-DMA stage the leaf streams */
-  uint8_t frid = 0;           /* emit ordered selection vectors */
-  uint16_t fnch = 64;         /* chunk capacity for the mask capture */
-  uint32_t fseg[4] = {};      /* per-leaf LDS segment bytes (staged mode) */
-};
-
-static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
-                                const dev_leaf *pl, jit_fstrategy &st) {
+bool jit_build_fstrategy(const obx_table_facts &h, const dev_plan_hdr &ph,
+                         const dev_leaf *pl, jit_fstrategy &st) {
   const char *e = getenv("OBX_JIT_V2");
   if (e && e[0] == '0') return false;
   if (ph.n_leaves == 0 || ph.n_leaves > 4) return false;
@@ -125,8 +110,7 @@ static bool jit_build_fstrategy(const obx_handle &h, const dev_plan_hdr &ph,
   return true;
 }
 
-static std::string jit_fstrategy_sig(const dev_plan_hdr &ph,
-                                     const jit_fstrategy &st) {
+std::string jit_fstrategy_sig(const dev_plan_hdr &ph, const jit_fstrategy &st) {
   std::string k = "F|";
   jit_emit(k, "s%d|r%d|u%d|g%d:%u:%u:%u:%u|i%d:%u|", st.nslice, st.r, st.fu,
            st.fstage, st.fseg[0], st.fseg[1], st.fseg[2], st.fseg[3], st.frid,
@@ -748,8 +732,8 @@ static void jit_f_direct_kernel(const dev_plan_hdr &ph,
        "}\n";
 }
 
-static std::string jit_gen_source_filter(const dev_plan_hdr &ph,
-                                         const jit_fstrategy &st) {
+std::string jit_gen_source_filter(const dev_plan_hdr &ph,
+                                  const jit_fstrategy &st) {
   std::string s;
   jit_f_prologue(ph, st, s);
   if (st.fstage) {

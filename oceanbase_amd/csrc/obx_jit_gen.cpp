@@ -1,7 +1,7 @@
-
 /*
- * obx_jit.inc — hipRTC-specialized kernels: shared infrastructure (included
- * by obx_engine.cpp).
+ * obx_jit_gen.cpp — hipRTC-specialized kernels: the generators and what
+ * they share. No HIP header and no device pointer: a table is its
+ * obx_table_facts. Declarations for the other units are in obx_jit.h.
  *
  * The precompiled kernels are plan-generic: the aggregate program is data
  * (dev_plan_hdr), so every row pays descriptor loads, operand-select chains
@@ -18,9 +18,11 @@
  * exact int128 arithmetic.
  *
  * This file holds what the generators share: the source emitter, the
- * packed-stream and leaf-test fragments, the embedded device headers, the
- * compile cache, plan-shape and block eligibility, compile-and-cache, and
- * choose / prepare / launch. The generators themselves, one file per kernel:
+ * packed-stream and leaf-test fragments, plan-shape and block eligibility,
+ * the launch grid, and choose / key / source of the scan kernel. The embedded
+ * device headers, the compile cache and prepare / launch are the hipRTC half,
+ * obx_jit_rt.cpp. The generators themselves, one file per kernel, included
+ * below:
  *   obx_jit_scan_v1.inc  scan, digit-split window accumulators (fallback
  *                        when the persistent kernel's bounds cannot be proven)
  *   obx_jit_scan.inc     scan, persistent accumulators (the Q1/Q6 hot path)
@@ -51,13 +53,16 @@
  *
  * OBX_JIT=0 disables; OBX_JIT_DUMP=<dir> writes the generated source
  * (obx_jit_src.hip, obx_jit_filter_src.hip) into that directory for offline
- * inspection, or into /tmp when it cannot be opened there (OBX_JIT_DUMP=1).
+ * inspection, or into /tmp when it cannot be opened there (OBX_JIT_DUMP=1);
+ * both are read in obx_jit_rt.cpp.
  */
-#include <hip/hiprtc.h>
-
 #include <cstdarg>
-#include <map>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
+
+#include "obx_jit.h"
 
 /* The source emitter: printf onto the end of a std::string. Two passes of
    vsnprintf, so the text is never cut; the format attribute keeps argument
@@ -97,36 +102,10 @@ __attribute__((format(printf, 1, 2))) static std::string jit_fmt(
   return s;
 }
 
-struct jit_entry {
-  hipModule_t mod = nullptr;
-  hipFunction_t fn = nullptr;
-  int wpb = 0; /* v2: workgroups per CU the launch grid is sized to */
-  bool bdesc = false;        /* v2: reads the packed block descriptors ... */
-  obx_bdesc_cols bd_cols = {}; /* ... of this ordered column list */
-  int joint = 0;             /* v2: joint-table form (obx_gpu_last_joint) */
-};
-
-struct jit_shape {
-  int n_vc = 0;
-  uint8_t vcol[4] = {0xFF, 0xFF, 0xFF, 0xFF}; /* schema column indices */
-  int n_wa = 0;
-  uint8_t agg_wa[OBX_DEV_MAX_AGGS];  /* 0xFF = COUNT(*) */
-  uint8_t agg_f2 = 0;                /* bit a: PROD2 fused with PROD3 mate */
-  bool has_mm = false;               /* MIN/MAX present: v2-only (the v1
-                                        generator has no CAS cells) */
-  /* value slot (vcol index) of a plan need index; -1 when there is none */
-  int slot(const dev_plan_hdr &ph, uint8_t need_idx) const {
-    if (need_idx == 0xFF) return -1;
-    for (int j = 0; j < n_vc; j++)
-      if (vcol[j] == ph.need_cols[need_idx]) return j;
-    return -1;
-  }
-};
-
 /* how a filter leaf is evaluated inline, from the load-time column facts;
    the scan kernel takes the first two, the filter kernel all three */
 enum { JL_NONE = 0, JL_RANGE = 1, JL_MASK = 2, JL_SET = 3 };
-static uint8_t jit_leaf_kind(const obx_handle &h, const dev_leaf &lf) {
+static uint8_t jit_leaf_kind(const obx_table_facts &h, const dev_leaf &lf) {
   /* multi-column black programs cannot lower to a ref mask */
   const bool mask_ok = lf.op != OBX_OP_BLACK || lf.n_bcols == 1;
   if (h.col_dict_any[lf.col] && mask_ok) return JL_MASK;
@@ -195,30 +174,47 @@ static void jit_emit_mask_test(std::string &s, int pad, const jit_leaf_ops &o,
              in.c_str(), o.mask.c_str(), field.c_str(), o.i);
 }
 
+/* grid of the persistent scan JIT (obx_jit_scan.inc): OBX_JIT_GRID_WAVES
+   times what is resident at wpb workgroups per CU, and never more
+   workgroups than blocks. Each workgroup flushes once, a handful of global
+   atomics per live cell, so the grid is free to be finer than the resident
+   set: the dispatcher then evens out CU-to-CU differences and the tail
+   shrinks to one short workgroup. Measured on Q1 SF=100 (profiles/
+   r03_q1_flush.md): 1x 3.00 ms, 2x 2.90, 4x 2.80, 8x 2.76, 12x 2.78,
+   16x 2.82, 32x 3.70; 1.5x (a half-empty second wave) 3.22. The one
+   source of that grid: the strategy proves its i64 accumulator bound for
+   it and the launch uses it. OBX_JIT_SGRID=n caps it at n workgroups (the
+   scan-side sibling of OBX_JIT_FGRID): small tables then give a workgroup
+   several blocks, which the block loop's tests and A/B runs need. */
+#define OBX_JIT_GRID_WAVES 8
+uint32_t jit_grid_for(uint32_t n_blocks, uint32_t n_cus, int wpb) {
+  uint64_t g = (uint64_t)(n_cus ? n_cus : 1) * (uint32_t)(wpb > 0 ? wpb : 1) *
+               OBX_JIT_GRID_WAVES;
+  if (const char *sg = getenv("OBX_JIT_SGRID")) {
+    const long v = atol(sg);
+    if (v >= 1 && (uint64_t)v < g) g = (uint64_t)v;
+  }
+  if (g > n_blocks) g = n_blocks;
+  return g ? (uint32_t)g : 1;
+}
+
+/* Rows one workgroup of that grid can sweep: its share of the blocks times
+   the rows of the largest block. The bound behind the i64 windows and the
+   row count packed into the joint cells. */
+static uint64_t jit_wg_rows(const obx_table_facts &h, uint32_t grid) {
+  if (!grid) grid = 1;
+  return (uint64_t)((h.n_blocks + grid - 1) / grid) *
+         (h.max_block_rows ? h.max_block_rows : 4096);
+}
+
 /* the generators: (plan, strategy) -> strategy signature and HIP source */
 #include "obx_jit_scan_v1.inc"
 #include "obx_jit_scan.inc"
 #include "obx_jit_filter.inc"
 
-static const char *OBX_JIT_SRC_DEV_H =
-#include "obx_embed_dev_h.inc"
-    ;
-static const char *OBX_JIT_SRC_COMMON_H =
-#include "obx_embed_common_h.inc"
-    ;
-static const char *OBX_JIT_SRC_JIT_DEV_H =
-#include "obx_embed_jit_dev_h.inc"
-    ;
-static const char *OBX_JIT_SRC_KEYSET_H =
-#include "obx_embed_keyset_h.inc"
-    ;
-
-static std::map<std::string, jit_entry> g_jit_cache;
-static int g_jit_kind = 0; /* 1 = v1 generator, 2 = v2 (persistent) */
-
 /* plan-shape eligibility + operand mapping (schema column indices, so the
    generated source carries cur.cols[<literal>]) */
-static bool jit_plan_shape(const dev_plan_hdr &ph, jit_shape &js) {
+bool jit_plan_shape(const dev_plan_hdr &ph, jit_shape &js) {
   if (ph.n_prog || ph.n_aggs == 0) return false;
   auto vc_add = [&](uint8_t need_idx) -> bool {
     if (need_idx == 0xFF) return true;
@@ -261,7 +257,7 @@ static bool jit_plan_shape(const dev_plan_hdr &ph, jit_shape &js) {
 
 /* largest per-block group-cell product of a two-column grouping: walked
    once per (handle, column pair), then served from the handle */
-static uint32_t jit_pair_cells_max(const obx_handle &h, uint8_t c0,
+static uint32_t jit_pair_cells_max(const obx_table_facts &h, uint8_t c0,
                                    uint8_t c1) {
   const uint32_t key = ((uint32_t)c0 << 16) | c1;
   auto it = h.pair_cells_max.find(key);
@@ -284,8 +280,8 @@ static uint32_t jit_pair_cells_max(const obx_handle &h, uint8_t c0,
    decisions are those of a walk over every block: group columns dict with
    count < 16 and at most 16 cells per block, value columns neither slow
    nor string. */
-static bool jit_blocks_ok(const obx_handle &h, const dev_plan_hdr &ph,
-                          const jit_shape &js) {
+bool jit_blocks_ok(const obx_table_facts &h, const dev_plan_hdr &ph,
+                   const jit_shape &js) {
   if (!h.lds_ok || h.col_class.empty()) return false;
   uint8_t gcol[2] = {0xFF, 0xFF};
   uint32_t cells = 1; /* product of the column maxima: an upper bound */
@@ -304,75 +300,8 @@ static bool jit_blocks_ok(const obx_handle &h, const dev_plan_hdr &ph,
   return true;
 }
 
-/* compile (or fetch) a generated kernel; nullptr on any failure (the caller
-   falls back to the precompiled kernels). gen_src() builds the source and
-   runs only on a cache miss; failures are cached too, so a plan that does
-   not compile costs one attempt. dump_name is the OBX_JIT_DUMP file and the
-   file name in the compile log. */
-template <class GenSrc>
-static jit_entry *jit_get(const std::string &key, GenSrc &&gen_src,
-                          const char *kernel, const char *dump_name,
-                          int wpb) {
-  auto it = g_jit_cache.find(key);
-  if (it != g_jit_cache.end())
-    return it->second.fn ? &it->second : nullptr;
-  jit_entry &ent = g_jit_cache[key]; /* fn stays null unless all succeeds */
-  ent.wpb = wpb;
-  const std::string src = gen_src();
-  if (const char *dump_dir = getenv("OBX_JIT_DUMP")) {
-    FILE *f = fopen((std::string(dump_dir) + "/" + dump_name).c_str(), "w");
-    if (!f) f = fopen((std::string("/tmp/") + dump_name).c_str(), "w");
-    if (f) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
-  }
-  hiprtcProgram prog;
-  const char *hdrs[4] = {OBX_JIT_SRC_COMMON_H, OBX_JIT_SRC_DEV_H,
-                         OBX_JIT_SRC_JIT_DEV_H, OBX_JIT_SRC_KEYSET_H};
-  const char *hdr_names[4] = {"obx_dev_common.h", "obx_dev.h",
-                              "obx_jit_dev.h", "obx_keyset.h"};
-  if (hiprtcCreateProgram(&prog, src.c_str(), dump_name, 4, hdrs,
-                          hdr_names) != HIPRTC_SUCCESS)
-    return nullptr;
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-                        "-DOBX_HIPRTC=1"};
-  if (hiprtcCompileProgram(prog, 4, opts) != HIPRTC_SUCCESS) {
-    size_t lsz = 0;
-    hiprtcGetProgramLogSize(prog, &lsz);
-    if (lsz > 1) {
-      std::string log(lsz, '\0');
-      hiprtcGetProgramLog(prog, &log[0]);
-      fprintf(stderr, "obx: JIT compile failed (%s):\n%s\n", kernel,
-              log.c_str());
-    }
-    hiprtcDestroyProgram(&prog);
-    return nullptr;
-  }
-  size_t csz = 0;
-  hiprtcGetCodeSize(prog, &csz);
-  std::string code(csz, '\0');
-  hiprtcGetCode(prog, &code[0]);
-  hiprtcDestroyProgram(&prog);
-  if (hipModuleLoadData(&ent.mod, code.data()) != hipSuccess ||
-      hipModuleGetFunction(&ent.fn, ent.mod, kernel) != hipSuccess) {
-    fprintf(stderr, "obx: JIT module load failed (%s)\n", kernel);
-    ent.fn = nullptr;
-    return nullptr;
-  }
-  return &ent;
-}
-
-/* Which scan kernel a plan gets, and everything its generator takes: the
-   one sequence shape -> blocks -> strategy -> v1 or v2 behind both
-   jit_prepare and the dump probe (obx_jit_dump_src_ex). */
-struct jit_scan_choice {
-  int kind = 0; /* 0 = no generated kernel, 1 = v1, 2 = v2 (persistent) */
-  jit_shape js;
-  jit_strategy st;    /* kind 2 */
-  jit_v1_strategy v1; /* kind 1 */
-};
-
-static int jit_scan_choose(const obx_handle &h, const dev_plan_hdr &ph,
-                           const dev_leaf *pl, bool force_v1,
-                           jit_scan_choice &c) {
+int jit_scan_choose(const obx_table_facts &h, const dev_plan_hdr &ph,
+                    const dev_leaf *pl, bool force_v1, jit_scan_choice &c) {
   if (!jit_plan_shape(ph, c.js) || !jit_blocks_ok(h, ph, c.js)) return 0;
   if (!force_v1) jit_build_strategy(h, ph, c.js, pl, c.st); /* !ok -> v1 */
   if (!c.st.ok && c.js.has_mm) return 0; /* v1 cannot do MIN/MAX */
@@ -381,73 +310,12 @@ static int jit_scan_choose(const obx_handle &h, const dev_plan_hdr &ph,
   return c.kind = c.st.ok ? 2 : 1;
 }
 
-static std::string jit_scan_key(const dev_plan_hdr &ph,
-                                const jit_scan_choice &c) {
+std::string jit_scan_key(const dev_plan_hdr &ph, const jit_scan_choice &c) {
   return jit_plan_sig(ph) +
          (c.kind == 2 ? jit_strategy_sig(ph, c.st) : jit_v1_sig(c.v1));
 }
 
-static std::string jit_scan_source(const dev_plan_hdr &ph,
-                                   const jit_scan_choice &c) {
+std::string jit_scan_source(const dev_plan_hdr &ph, const jit_scan_choice &c) {
   return c.kind == 2 ? jit_gen_source_v2(ph, c.js, c.st)
                      : jit_gen_source(ph, c.js, c.v1);
-}
-
-/* prepare (compile/lookup) before the timed region; nullptr = use the
-   precompiled kernels */
-static jit_entry *jit_prepare(const obx_handle &h, const dev_plan_hdr &ph,
-                              const dev_leaf *pl) {
-  const char *e = getenv("OBX_JIT");
-  if (e && e[0] == '0') return nullptr;
-  jit_scan_choice c;
-  if (!jit_scan_choose(h, ph, pl, false, c)) return nullptr;
-  g_jit_kind = c.kind;
-  jit_entry *je = jit_get(
-      jit_scan_key(ph, c), [&] { return jit_scan_source(ph, c); },
-      "k_jit_scan", "obx_jit_src.hip", c.kind == 2 ? c.st.wpb : 0);
-  if (je && c.kind == 2) { /* the signature carries both: same for every hit */
-    je->bdesc = c.st.bdesc != 0;
-    je->bd_cols = c.st.bd_cols;
-    je->joint = jit_joint_form_of(c.st);
-  }
-  return je;
-}
-
-static jit_entry *jit_prepare_filter(const obx_handle &h,
-                                     const dev_plan_hdr &ph,
-                                     const dev_leaf *pl, int want_row_ids) {
-  const char *e = getenv("OBX_JIT");
-  if (e && e[0] == '0') return nullptr;
-  jit_fstrategy st;
-  if (!jit_build_fstrategy(h, ph, pl, st)) return nullptr;
-  if (want_row_ids) {
-    /* ordered selection vectors need the per-block mask capture of the
-       staged kernel and a bounded chunk count for the LDS mask array */
-    uint32_t nch = ((h.max_block_rows ? h.max_block_rows : 4096) + 63) / 64;
-    if (!st.fstage || nch > 256) return nullptr;
-    st.frid = 1;
-    st.fnch = (uint16_t)nch;
-  }
-  return jit_get(
-      jit_fstrategy_sig(ph, st), [&] { return jit_gen_source_filter(ph, st); },
-      "k_jit_filter", "obx_jit_filter_src.hip", 0);
-}
-
-static int jit_launch(jit_entry *je, obx_handle &h, const obx_bdesc *bd,
-                      hipStream_t stream, uint32_t *grid_out) {
-  /* v2 keeps its accumulators for the kernel's lifetime and flushes once
-     per workgroup: its grid is a multiple of the resident set (the grid
-     the strategy proved its i64 bound for); v1 merges per block and keeps
-     the fixed grid */
-  const uint32_t grid = je->wpb ? jit_grid_for(h.n_blocks, h.n_cus, je->wpb)
-                                : grid_for(h.n_blocks);
-  *grid_out = grid;
-  /* the v2 kernel takes the descriptor array last (null when its strategy
-     reads dev_block); v1 has no such parameter and ignores the entry */
-  void *args[8] = {&h.d_buf,     &h.d_blocks, &h.n_blocks,   &h.d_pleaves,
-                   &h.d_bleaves, &h.d_gtable, &h.d_counters, &bd};
-  return hipModuleLaunchKernel(je->fn, grid, 1, 1, OBX_WG_HOST, 1, 1, 0,
-                               stream, args, nullptr) == hipSuccess
-             ? 0
-             : -1;
 }

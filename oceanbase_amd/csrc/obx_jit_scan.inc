@@ -1,6 +1,7 @@
 /*
  * obx_jit_scan.inc — second-generation (persistent-accumulator) scan
- * codegen: strategy, strategy signature, source (included by obx_jit.inc).
+ * codegen: strategy, strategy signature, source (included by
+ * obx_jit_gen.cpp; the strategy struct itself is in obx_jit.h).
  *
  * Defaults, all measured best (profiles/r02_*, profiles/r03_q1_flush.md):
  * R=4 strip mining, 4 accumulator stripes, single-axis joint histogram
@@ -9,7 +10,7 @@
  * OBX_JIT_JPACK=0 keeps the count in a histogram of its own), jcells-sized
  * LDS, striped counter slots,
  * in-workgroup flush reduction, launch grid 8x the resident set
- * (jit_grid_for, obx_engine.cpp — also the grid of the i64 window bound),
+ * (jit_grid_for, obx_jit_gen.cpp — also the grid of the i64 window bound),
  * 32-bit extraction of packed streams with r * width <= 32 (OBX_JIT_M32=0
  * restores the 64-bit reads), one multiply against a combined u32 factor
  * table for a PROD3 term whose operands are proven to fit (OBX_JIT_CTAB=0
@@ -42,7 +43,7 @@
  * per-row cost was dominated by the exact-int128 digit-split LDS atomics
  * (4 atomics + guards per aggregate per row) and per-row dict-entry
  * lookups. V2 removes both, using the load-time column summaries (min/max
- * skip index, dict-everywhere flags — obx_engine.cpp):
+ * skip index, dict-everywhere flags — obx_table_facts, obx_facts.h):
  *
  *  - i64 window accumulators: when the per-block sum provably fits int64
  *    (max|term| x max_block_rows < 2^62, bounds from the stored min/max),
@@ -74,7 +75,7 @@
  * digit-split path) or the precompiled kernels. OBX_JIT_V2=0 forces v1.
  *
  * Layout: jit_build_strategy (the only place that reads the environment;
- * knob -> field list in obx_jit.inc), jit_strategy_sig, the fragments the
+ * knob -> field list in obx_jit_gen.cpp), jit_strategy_sig, the fragments the
  * phases share (packed read, mask, field, product operand, one copy each),
  * then one function per kernel phase; jit_gen_source_v2 at the end lists
  * them in kernel order.
@@ -91,101 +92,6 @@ enum {
   JA_HISTMM = 6,     /* min/max over dict entries with live hist counts */
 };
 
-struct jit_vtab {          /* per-block LDS value table over dict refs */
-  uint8_t vc = 0;          /* value-col slot (js.vcol index) */
-  uint8_t kind = 0;        /* 0 ident, 1 (one - e), 2 (one + e) */
-  int64_t one = 0;
-  uint32_t dim = 0;        /* maxcnt + 1 */
-};
-
-/* per-aggregate slot ids of a strategy: -1 = none */
-struct jit_agg_ids {
-  int8_t v[OBX_DEV_MAX_AGGS];
-  jit_agg_ids() { for (int8_t &x : v) x = -1; }
-  int8_t &operator[](size_t a) { return v[a]; }
-  const int8_t &operator[](size_t a) const { return v[a]; }
-};
-
-struct jit_strategy {
-  bool ok = false;
-  uint8_t vmode[4] = {};     /* JV_CTX / JV_REF per value col */
-  uint8_t vext[4] = {};      /* CTX col can be NULL (ext) in some block */
-  uint8_t vraw8[4] = {};     /* CTX col is aligned 8-B RAW in every block */
-  uint32_t vdim[4] = {};     /* REF: maxcnt+1 */
-  uint8_t astrat[OBX_DEV_MAX_AGGS] = {};
-  jit_agg_ids wa64;    /* JA_I64*: wacc64 slot */
-  jit_agg_ids amm;     /* JA_MM: wmm slot */
-  int n_mm = 0;
-  jit_agg_ids ahist;   /* JA_HIST/HCOUNT: hist id */
-  jit_agg_ids atab_b;  /* product b operand: table id or -1 */
-  jit_agg_ids atab_c;  /* product c operand: table id or -1 */
-  jit_agg_ids aval_a;  /* a operand: value-col slot or -1 */
-  jit_agg_ids atab_a;  /* a operand via ident table: id or -1 */
-  int n_w64 = 0;
-  int n_hist = 0;
-  uint8_t hist_vc[4] = {};   /* hist id -> value-col slot */
-  int8_t hist_tab[4] = {};   /* hist id -> ident table id (entry weights) */
-  uint32_t hist_off[4] = {}; /* u32 offsets into the shared hist array */
-  uint32_t hist_total = 0;   /* total u32 slots */
-  int n_tab = 0;
-  jit_vtab tabs[6] = {};
-  uint8_t leaf_inline = 0;   /* ALL leaves inline-evaluable in the sweep */
-  uint8_t leaf_kind[8] = {}; /* JL_RANGE or JL_MASK */
-  uint16_t leaf_cols[8] = {};
-  uint8_t r = 1;             /* rows per lane (strip mining) */
-  uint8_t stripes = 4;       /* i64 accumulator lane stripes */
-  uint32_t stage_bytes = OBX_LDS_STAGE_BYTES + 32;
-  uint8_t leaf_multi[8] = {}; /* r entries per packed read */
-  uint8_t g_multi[2] = {};
-  uint8_t v_multi[4] = {};
-  /* ... and that read fits 32 bits (r * max_width <= 32): one
-     v_alignbit_b32 over two dwords, 32-bit shifts and masks per field */
-  uint8_t leaf_m32[8] = {};
-  uint8_t g_m32[2] = {};
-  uint8_t v_m32[4] = {};
-  int8_t cnt_hist = -1;      /* cell counts derived from this hist (drops
-                                the per-row wcnt atomic) */
-  uint32_t jcells = 16;      /* group-cell rows actually possible */
-  /* weighted joint histogram: SUM / SUM_PROD* family sharing one CTX
-     weight column with small-dict REF factors collapses to a single
-     per-row LDS add into wsum[cell][d0][d1]; the factor products are
-     applied at flush (generalizes ObVectorStore::do_group_by's
-     count-only dict pushdown to value-weighted cells) */
-  uint8_t jws_on = 0;
-  int8_t jws_ja = -1;                       /* weight value-col slot */
-  int8_t jws_a0 = -1, jws_a1 = -1;          /* axis value-col slots */
-  uint32_t jws_d0 = 1, jws_d1 = 1;          /* axis dims */
-  uint32_t jws_cells = 16;                  /* group-cell rows */
-  uint8_t jws_member[OBX_DEV_MAX_AGGS] = {};
-  jit_agg_ids jws_f0;                       /* flush factor tab / axis0 */
-  jit_agg_ids jws_f1;                       /* flush factor tab / axis1 */
-  /* row count packed into the joint cell: when the weight is proven
-     non-negative, never NULL, and its sum over the rows one workgroup can
-     sweep stays below 2^jws_shift, each row adds weight + (1 << jws_shift),
-     so a cell carries its row count above the weight sum. A joint-axis
-     column then needs no histogram of its own: the aggregates that read
-     one (SUM, COUNT(col), MIN/MAX) take the counts of their axis
-     (jws_cax) at flush, weighted through the ident table jws_ctab */
-  uint8_t jws_pack = 0;
-  uint8_t jws_shift = 0;
-  jit_agg_ids jws_cax;                      /* 0 / 1: counts along that axis */
-  jit_agg_ids jws_ctab;                     /* ident table of that axis col */
-  /* narrowed PROD3: when the weight is a CTX column proven in [0, 2^32)
-     and both dict factors are proven non-negative with a product below
-     2^32, the per-row term is ONE u32 x u32 -> u64 multiply against a
-     combined LDS table vtc[xb][xc] = (one_b - eb) * (one_c + ec), instead
-     of two 64 x 64 multiplies over two table reads */
-  int8_t ctab_agg = -1;
-  uint32_t ctab_db = 0, ctab_dc = 0;
-  uint32_t lds_bytes = 0;
-  int wpb = 7;
-  /* per-block geometry from the packed descriptor (obx_bdesc) instead of
-     dev_block; bd_cols is the descriptor's column list, need_cols then the
-     leaf columns not among them */
-  uint8_t bdesc = 0;
-  obx_bdesc_cols bd_cols = {};
-};
-
 /* slot of a schema column in the strategy's descriptor list (it is there:
    jit_build_strategy lists every column the block loop reads) */
 static int jit_bd_slot(const jit_strategy &st, uint16_t col) {
@@ -195,7 +101,7 @@ static int jit_bd_slot(const jit_strategy &st, uint16_t col) {
 }
 
 /* max |value| of a column from the stored bounds; false if unknown */
-static bool jit_col_maxabs(const obx_handle &h, uint16_t col, uint64_t *out) {
+static bool jit_col_maxabs(const obx_table_facts &h, uint16_t col, uint64_t *out) {
   if (!h.col_known[col]) return false;
   if (h.col_min[col] > h.col_max[col]) { *out = 0; return true; } /* empty */
   uint64_t a = h.col_min[col] == INT64_MIN
@@ -243,7 +149,7 @@ static int jit_hist_get(jit_strategy &st, uint8_t vc, uint32_t dim) {
    that first) */
 enum { JB_OK = 0, JB_NO_V2 = 1, JB_PACK_REFUSED = 2 };
 
-static int jit_build_strategy_form(const obx_handle &h,
+static int jit_build_strategy_form(const obx_table_facts &h,
                                    const dev_plan_hdr &ph,
                                    const jit_shape &js, const dev_leaf *pl,
                                    bool want_pack, jit_strategy &st) {
@@ -772,7 +678,7 @@ static int jit_build_strategy_form(const obx_handle &h,
    where that can be proven, else without. A refused form leaves nothing
    behind: the other is built from scratch, so it is exactly the strategy
    OBX_JIT_JPACK=0 gives directly. */
-static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
+static bool jit_build_strategy(const obx_table_facts &h, const dev_plan_hdr &ph,
                                const jit_shape &js, const dev_leaf *pl,
                                jit_strategy &st) {
   const char *pe = getenv("OBX_JIT_JPACK");
@@ -789,7 +695,7 @@ static bool jit_build_strategy(const obx_handle &h, const dev_plan_hdr &ph,
 }
 
 /* what obx_gpu_last_joint reports of a strategy */
-static int jit_joint_form_of(const jit_strategy &st) {
+int jit_joint_form_of(const jit_strategy &st) {
   if (!st.jws_on) return 0;
   if (!st.jws_pack) return 1;
   return st.jws_a1 >= 0 ? 3 : 2;

@@ -1,6 +1,6 @@
 /*
  * obx_jit_scan_v1.inc — first-generation scan codegen (included by
- * obx_jit.inc): the fallback for plans whose bounds the persistent kernel
+ * obx_jit_gen.cpp): the fallback for plans whose bounds the persistent kernel
  * (obx_jit_scan.inc) cannot prove, or under OBX_JIT_V2=0.
  *
  * Eligible plans: AND-only filter, SUM-family aggregates over <= 4 distinct
@@ -13,14 +13,6 @@
  * jit_gen_source lists the kernel's phases: header, per-block preamble,
  * sweep, merge. Each takes (plan, shape, strategy, out).
  */
-
-/* all the v1 kernel takes beyond the plan: the waves-per-block floor. 7
-   WGs/CU measured best for the Q1/Q6 shapes (LDS ~22 KB, ~72 VGPRs);
-   OBX_JIT_WPB overrides for experiments (read by jit_scan_choose, pasted
-   as given) */
-struct jit_v1_strategy {
-  std::string wpb = "7";
-};
 
 static std::string jit_v1_sig(const jit_v1_strategy &st) {
   return "V1|p" + st.wpb + "|";
